@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark: Mrays/s of 1920x1080 primary rays (+ BVH build ms) on 1..8 MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|filled] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|filled] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-extra] [--pmc on|off]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 Workload: BASELINE.json's own configs. N = 1 (default): C3 = configs[2], north_star's target config
@@ -13,6 +14,14 @@ C4's one-GPU figure (`c4_armadillo_4k`) as the curve's first point, beside C2 (b
 the filled view and C5 (merged 1.1M-triangle proxy + shadow rays). A step = one primary-ray trace of
 the whole frame with the BVH resident in HBM (inputs resident before the timed region).
 --config picks another workload for `value`.
+
+A plain run (N = 1, no --full) does only what `value` needs: it builds the scene, warms up, times the
+--steps frames and prints the line (`value`, `ms_per_step`, `build_ms`, the config). Everything else
+described below — the counter passes and rooflines, the traversal counters, the same frame one trace at a
+time, the frame check, the other configs, reference mode, the hashed grid, the aa.xml workload, the CPU
+baseline and the full record file — is measured only with --full. --dump-outputs DIR writes the planes the
+last timed step traced (what a caller reads back from its render target) as DIR/<plane>.npy, with or
+without --full.
 
 N = 1: frames in flight (--frames-in-flight, default 3): consecutive steps trace into alternating
 render targets, each on its own HIP stream (bm_rt_set_stream), so one frame's trace starts while
@@ -29,7 +38,7 @@ BM_BENCH_SHARED_DEVICE=1 rehearses N ranks on one GPU (RCCL refuses two ranks on
 bands then travel through torch.distributed over gloo (host memory). Rank 0 checks the assembled
 frame against its own single-device trace after the timed region (`frame_check`).
 
-One JSON line on rank 0 (driver contract), with `roofline` (dominant kernel: the trace) and
+One JSON line on rank 0 (driver contract), with (N = 1: under --full) `roofline` (dominant kernel: the trace) and
 `cpu_baseline` (the reference's own algorithm — kd-tree build + first-hit-leaf march, restated in
 oracle/ — on the host cores). Roofline fields:
 * `traffic` = HBM bytes per launch (one frame) from PMC counters measured LIVE on this run's code (N = 1:
@@ -95,6 +104,15 @@ def parse():
                          "'all': packed+tri+t+nz as traced (16 B/px)")
     ap.add_argument("--frames-in-flight", type=int, default=3,
                     help="render targets, each on its own HIP stream (1: every frame on the context stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: beside the headline also the counter passes and rooflines, the traversal counters, "
+                         "one frame at a time, the frame check, the side figures (other configs, reference mode, "
+                         "hashed grid, aa.xml), the CPU baseline and the full record file; --no-cpu-baseline, "
+                         "--no-extra, --pmc and --cpu-seconds choose among them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the planes of the last timed step's render target as "
+                         "DIR/<plane>.npy (float32 / float64; a fixed seeded pixel sample when the planes "
+                         "exceed 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the side figures (other configs, modes)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
@@ -302,6 +320,32 @@ def cpu_baseline(meshes, width, height, cam, eye, orient, seconds, bvh_width=4):
                           "note": "scalar LBVH of oracle/ (this build's GPU algorithm, same arithmetic)"}}
 
 
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: all planes together stay under 64 MB
+DUMP_SEED = 20240607
+DUMP_MISS_T = -1.0  # --dump-outputs: a pixel without a hit has t = +inf in the render target; the files hold this
+
+
+def dump_outputs(out_dir, planes):
+    """--dump-outputs: the planes a caller reads back from the render target of the last timed step, one
+    DIR/<name>.npy each. The integer planes (packed colour, triangle id: 32 bits) go out as float64 and
+    the float planes as float32, both exact. Every value written is finite: t of a pixel without a hit
+    (+inf in the render target; its triangle id is 0xFFFFFFFF) is written as DUMP_MISS_T, below every hit's
+    t >= 0. When the planes together exceed DUMP_MAX_BYTES, every plane
+    keeps the same fixed, seeded sample of pixels (sorted pixel indices, so runs and builds compare
+    sample for sample). Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {name: np.asarray(a, np.float32 if a.dtype == np.float32 else np.float64) for name, a in planes.items()}
+    out = {name: np.where(np.isfinite(a), a, a.dtype.type(DUMP_MISS_T)) for name, a in out.items()}
+    h, w = next(iter(out.values())).shape[:2]
+    per_pixel = sum(a.nbytes for a in out.values()) // (h * w)
+    if h * w * per_pixel > DUMP_MAX_BYTES:  # (H, W, ...) planes -> (sample, ...)
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, DUMP_MAX_BYTES // per_pixel, replace=False))
+        out = {name: a.reshape((h * w,) + a.shape[2:])[keep] for name, a in out.items()}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def hits_of(packed):
     return int((packed != 0x0000FF00).sum())
 
@@ -309,7 +353,8 @@ def hits_of(packed):
 class Workload:
     """One config on one device: scene (built), camera, counters and their algorithmic bytes."""
 
-    def __init__(self, ctx, name, torch, stream):
+    def __init__(self, ctx, name, torch, stream, counters=True):
+        """counters=False (a plain run): no counting trace and no record export, so no rooflines."""
         from raytracercuda_amd import beam, scenes
         self.beam, self.scenes, self.torch, self.stream = beam, scenes, torch, stream
         self.ctx, self.name = ctx, name
@@ -325,16 +370,20 @@ class Workload:
         self.st = self.scene.last_stats
         self.nverts = sum(int(np.asarray(m["pos"]).reshape(-1, 3).shape[0]) for m in self.meshes)
         # the BVH4 records a traversal can reach (the product's part of the records the build writes)
-        self.reachable = len(beam.reachable_records(self.scene.export()[0])) if self.st["bvh_width"] == 4 else None
+        self.reachable = (len(beam.reachable_records(self.scene.export()[0]))
+                          if counters and self.st["bvh_width"] == 4 else None)
         self.cam = beam.ICamera.create(ctx)
         ctx._check(self.cam.setInitialRays(self.W, self.H, *c["rays"]))
+        self.rays = self.W * self.H
+        self.counters, self.bytes, self.last = None, 0, None
+        if not counters:
+            return
         rt = beam.IRenderTarget.createOffscreen(ctx, self.W, self.H)
         if self.light:
             self.counters = self.cam.traceShadowCounters(self.eye, self.orient, self.scene, rt, self.light)
         else:
             self.counters = self.cam.traceCounters(self.eye, self.orient, self.scene, rt)
         rt.destroy()
-        self.rays = self.W * self.H
         self.bytes = algorithmic_bytes(self.counters, self.rays, self.st["bvh_width"])
         if self.light:
             self.bytes += shadow_bytes(self.counters)
@@ -402,11 +451,20 @@ class Workload:
         """Frames in flight and one frame at a time, each with its roofline, and the in-flight frame
         checked bit for bit against a trace on the context stream. only="inflight"/"single" (profiling
         runs) times one of the two and reports it in both places. pmc: the live counter summary
-        (segments "<config>/inflight", "<config>/single")."""
+        (segments "<config>/inflight", "<config>/single"). A workload made with counters=False (a plain
+        run) times the steps once and reports the headline figures alone."""
         if only == "single":
             nbuf = 1
         step_ms, kern_ms, last = self.run(nbuf, steps, warmup)
         kind = self.kind
+        self.last = last  # the planes of the last step timed for `value` (--dump-outputs)
+        if self.counters is None:
+            return {"scene": self.cfg["scene"], "tris": self.st["num_tris"], "width": self.W, "height": self.H,
+                    "eye": list(self.eye), "build_ms": self.build_ms, "build_roofline": None,
+                    "frames_in_flight": nbuf, "mrays_s": self.rays / (step_ms / 1e3) / 1e6, "ms_per_step": step_ms,
+                    "trace_kernel_ms": kern_ms, "frame_hits": hits_of(last["packed"]), "frame_check": None,
+                    "trace_kind": kind, "roofline": None, "single_frame": None, "per_ray": None,
+                    **({"light": list(self.light)} if self.light else {})}
         if only == "both":
             ref = self.reference_frame()
             check = all(np.array_equal(last[k], ref[k]) for k in ref)
@@ -679,11 +737,11 @@ def live_counters(args):
     """The counter passes (tools/pmc.py) for this run, before this process touches the GPU."""
     from tools import pmc as tpmc
     child = [a for a in sys.argv[1:]]
-    for flag in ("--pmc", "--pmc-keep", "--steps", "--warmup", "--cpu-seconds"):  # drop flag + value
+    for flag in ("--pmc", "--pmc-keep", "--steps", "--warmup", "--cpu-seconds", "--dump-outputs"):  # drop flag + value
         while flag in child:
             i = child.index(flag)
             del child[i:i + 2]
-    child = [a for a in child if not a.startswith(("--pmc=", "--pmc-keep=", "--steps=", "--warmup="))]
+    child = [a for a in child if not a.startswith(("--pmc=", "--pmc-keep=", "--steps=", "--warmup=", "--dump-outputs="))]
     child += ["--no-cpu-baseline"]
     t0 = time.perf_counter()
     summary, note = tpmc.run_live(os.path.join(REPO, "bench.py"), child, keep_dir=args.pmc_keep,
@@ -707,11 +765,13 @@ def pmc_report(pmc, note):
 def single_gpu(args, torch, stream, pmc=None):
     from raytracercuda_amd import beam, scenes
     ctx = beam.Context(params=BENCH_PARAMS, device=0, stream=stream.cuda_stream, leaf_size=args.leaf_size, bvh_width=args.bvh_width)
-    wl = Workload(ctx, args.config, torch, stream)
+    wl = Workload(ctx, args.config, torch, stream, counters=args.full)
     nbuf = max(1, args.frames_in_flight)
     head = wl.measure(nbuf, args.steps, args.warmup, args.only, pmc=pmc)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl.last)
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         for name, key in EXTRA_CONFIGS.items():
             if name == args.config:
                 continue
@@ -730,7 +790,7 @@ def single_gpu(args, torch, stream, pmc=None):
         extra["hashed_grid"]["config_id"] = REFMODE_CONFIG
         extra["aa_xml"] = aa_xml_figure(ctx, stream, torch, max(1, args.frames_in_flight))
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         c = scenes.CONFIGS[args.config]
         cpu = cpu_baseline(wl.meshes, wl.W, wl.H, c["rays"], wl.eye, wl.orient, args.cpu_seconds,
                            wl.st["bvh_width"])
@@ -858,6 +918,8 @@ def multi_gpu(args, torch, dist, rank, world, local, shared):
             elif light:
                 got["shadow"] = last.readShadow()
         check = all(np.array_equal(got[k], full[k]) for k in got)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, got)
         for h in (r1, c1, s1):
             h.destroy()
         del k1
@@ -1171,7 +1233,7 @@ def main():
         pmc_child(args, torch, torch.cuda.current_stream())
         return
     pmc, pmc_note = None, "off"
-    if world == 1 and (args.pmc == "on" or (args.pmc == "auto" and args.only == "both")):
+    if world == 1 and args.full and (args.pmc == "on" or (args.pmc == "auto" and args.only == "both")):
         from tools import pmc as tpmc
         if tpmc.under_profiler():
             pmc_note = "skipped: already running under a profiler"
@@ -1199,7 +1261,7 @@ def main():
         stream = torch.cuda.current_stream()
         head, extra, cpu = single_gpu(args, torch, stream, pmc)
         full = finite(single_record(args, head, extra, cpu, pmc, pmc_note, common))
-        print(json.dumps(compact_record(full, write_full(full)), allow_nan=False), flush=True)
+        print(json.dumps(compact_record(full, write_full(full) if args.full else None), allow_nan=False), flush=True)
         return
     rec = multi_gpu(args, torch, dist, rank, world, local, shared)
     if rank == 0:

@@ -3,6 +3,8 @@ N > 1 and N = 1 JSON lines (from synthetic per-rank records; the GPU runs fill t
 import argparse
 import json
 
+import pytest
+
 import bench
 
 
@@ -247,6 +249,65 @@ def test_nonfinite_values_become_null():
         {"a": None, "b": [None, 1.0], "c": {"d": None}}
 
 
+def test_dump_outputs_planes_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float .npy per plane, exact (32-bit integer planes as float64, float planes as
+    float32, t = +inf of a miss as -1); planes over the byte budget keep one fixed seeded pixel sample, the same in every plane and run."""
+    import numpy as np
+    rng = np.random.default_rng(1)
+    h, w = 37, 53  # odd sizes
+    planes = {"packed": rng.integers(0, 2**32, (h, w), dtype=np.uint64).astype(np.uint32),
+              "tri_id": np.full((h, w), 0xFFFFFFFF, np.uint32), "t": rng.random((h, w), dtype=np.float32),
+              "rgb": rng.random((h, w, 3), dtype=np.float32)}
+    planes["t"][0, 0] = np.inf  # a miss
+    shapes = bench.dump_outputs(str(tmp_path / "a"), planes)
+    assert shapes == {"packed": [h, w], "tri_id": [h, w], "t": [h, w], "rgb": [h, w, 3]}
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in planes}
+    assert got["packed"].dtype == got["tri_id"].dtype == np.float64 and got["t"].dtype == got["rgb"].dtype == np.float32
+    assert got["t"][0, 0] == bench.DUMP_MISS_T == -1.0  # the miss: finite in the file
+    want = dict(planes, t=np.where(np.isinf(planes["t"]), np.float32(-1.0), planes["t"]))
+    for k in planes:
+        assert np.isfinite(got[k]).all() and np.array_equal(got[k], want[k])
+    # a budget of 32 B/pixel x 500 pixels: every plane keeps the same 500 pixels, in pixel order
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 500 * (8 + 8 + 4 + 12))
+    for d in ("b", "c"):
+        shapes = bench.dump_outputs(str(tmp_path / d), planes)
+        assert shapes == {"packed": [500], "tri_id": [500], "t": [500], "rgb": [500, 3]}
+    b = {k: np.load(tmp_path / "b" / (k + ".npy")) for k in planes}
+    for k in planes:
+        assert np.array_equal(b[k], np.load(tmp_path / "c" / (k + ".npy")))
+    flat_t = want["t"].reshape(-1)
+    px = np.nonzero(np.isin(flat_t, b["t"]))[0]  # random floats: the sampled pixels are identifiable by t
+    assert len(px) == 500
+    assert np.array_equal(b["packed"], planes["packed"].reshape(-1)[px])
+    assert np.array_equal(b["rgb"], planes["rgb"].reshape(-1, 3)[px])
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_plain_record_has_the_headline_fields():
+    """A plain run's head (no counters, rooflines, single frame or side figures) still makes the line."""
+    a = _args()
+    bench.resolve_config(a, 1)
+    head = {"mrays_s": 30000.0, "ms_per_step": 0.069, "scene": "armadillo_proxy", "tris": 278520, "width": 1920,
+            "height": 1080, "frames_in_flight": 3, "build_ms": 0.1, "build_roofline": None, "trace_kind": "cull+quads",
+            "trace_kernel_ms": 0.2, "roofline": None, "single_frame": None, "per_ray": None,
+            "frame_hits": 1, "frame_check": None}
+    full = bench.finite(bench.single_record(a, head, {}, None, None, "off", _common(1)))
+    out = json.loads(json.dumps(bench.compact_record(full, None), allow_nan=False))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in out
+    assert out["value"] == 30000.0 and out["ms_per_step"] == 0.069 and out["build_ms"] == 0.1
+    assert out["roofline"] is None and out["cpu_baseline"] is None and "side" not in out and "full_record" not in out
+
+
 def _run_bench(args, extra_env):
     import os
     import subprocess
@@ -256,6 +317,42 @@ def _run_bench(args, extra_env):
         env.pop(k, None)
     return subprocess.run([sys.executable, bench.__file__, *args], capture_output=True, text=True, env=env,
                           timeout=240, cwd=os.path.dirname(bench.__file__))
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_prints_the_line_and_dumps_the_traced_frame(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (C2, the bunny at 1080p): one line with K
+    timed steps and no figure of --full, and the dumped planes are the frame a trace of that config gives."""
+    import numpy as np
+
+    from raytracercuda_amd import beam, scenes
+    out = tmp_path / "planes"
+    p = _run_bench(["--gpus", "1", "--steps", "4", "--warmup", "2", "--config", "c2", "--dump-outputs", str(out)], {})
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout
+    rec = json.loads(lines[0])
+    assert rec["metric"] == bench.METRIC and rec["unit"] == "Mrays/s" and rec["higher_is_better"] is True
+    assert rec["n_gpus"] == 1 and rec["steps"] == 4 and rec["warmup"] == 2 and rec["dtype"] == "f32"
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["build_ms"] > 0
+    assert abs(rec["value"] - 1920 * 1080 / (rec["ms_per_step"] / 1e3) / 1e6) <= 1e-4 * rec["value"]
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and "side" not in rec and "full_record" not in rec
+    c = scenes.CONFIGS["c2"]
+    ctx = beam.Context(device=0)
+    frame, _ = beam.render(ctx, scenes.scene(c["scene"]), c["width"], c["height"], c["rays"], c["eye"], scenes.IDENTITY)
+    ctx.close()
+    # the same planes (at 1080p: the same seeded pixel sample of them) as this process's own trace gives
+    shapes = bench.dump_outputs(str(tmp_path / "own"), frame)
+    assert sorted(shapes) == ["packed", "rgb", "t", "tri_id"]
+    for k, dt in (("packed", np.float64), ("tri_id", np.float64), ("t", np.float32), ("rgb", np.float32)):
+        got = np.load(out / (k + ".npy"))
+        assert got.dtype == dt and list(got.shape) == shapes[k] and np.isfinite(got).all(), k
+        assert np.array_equal(got, np.load(tmp_path / "own" / (k + ".npy"))), k
+    assert rec["frame_hits"] == bench.hits_of(frame["packed"])
+    # t: the traced value at the sampled hits, -1 at the misses (tri_id 0xFFFFFFFF), which the view has
+    t, tri = np.load(out / "t.npy"), np.load(out / "tri_id.npy")
+    assert ((t == -1.0) == (tri == 0xFFFFFFFF)).all() and (t == -1.0).any() and (t[t != -1.0] > 0).all()
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64_000_000
 
 
 def test_gpus_n_self_launches_n_ranks():

@@ -7,7 +7,7 @@ OUT=gpurun_out/$1; CFGS=$2; shift 2; mkdir -p "$OUT"
 for round in 1 2; do
 for cfg in $CFGS; do
   for lib in "$@"; do
-    BEAM_HIP_LIB="$lib" timeout -k 10 120 python bench.py --config $cfg --no-extra --no-cpu-baseline --steps 40 --warmup 10 \
+    BEAM_HIP_LIB="$lib" timeout -k 10 120 python bench.py --full --config $cfg --no-extra --no-cpu-baseline --steps 40 --warmup 10 \
       > "$OUT/tmp.json" 2>> "$OUT/err.log"
     rc=$?; if [ $rc -ne 0 ]; then echo "rc=$rc $cfg $lib" >> "$OUT/ab.log"; exit $rc; fi
     python - "$OUT/tmp.json" "$cfg" "$lib" >> "$OUT/ab.log" <<'PY'

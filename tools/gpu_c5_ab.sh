@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd); OUT=$1; shift; mkdir -p "gpurun_out/$OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 CFG=${AB_CFG:-c5}
-ARGS="--config $CFG --only single --no-extra --no-cpu-baseline --warmup 5"
+ARGS="--full --config $CFG --only single --no-extra --no-cpu-baseline --warmup 5"
 for l in "$@"; do
   for ctr in WRITE_SIZE FETCH_SIZE; do
     (cd /tmp && export TMPDIR=/tmp && BEAM_HIP_LIB="$ROOT/raytracercuda_amd/$l" timeout -s KILL 120 rocprofv3 --pmc $ctr \

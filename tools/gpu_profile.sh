@@ -14,7 +14,7 @@ OUT="$ROOT/gpurun_out/$TAG"; mkdir -p "$OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 python -c "import sys; sys.path.insert(0, '.'); from raytracercuda_amd import build; print(build.source_stamp())" > "$OUT/stamp.txt"
 fatal() { local rc=$1; [ "$rc" -ge 124 ] || [ "$rc" -eq 134 ] || [ "$rc" -eq 139 ]; }
-BENCH_ARGS="--no-extra --no-cpu-baseline --steps 30 --warmup 5"
+BENCH_ARGS="--full --no-extra --no-cpu-baseline --steps 30 --warmup 5"
 for cfg in $CONFIGS; do
   D="$OUT/$cfg"; mkdir -p "$D"
   for mode in single inflight; do

@@ -29,7 +29,7 @@ if [ "${L2CAL:-0}" = "1" ]; then  # L1 -> L2 request size (tools/pmc.py L2_REQ_B
   step l2_calib 120 python tools/l2_calib.py "$OUT/l2_calib"
 fi
 if [ "${BENCH:-1}" = "1" ]; then  # the driver's own command line
-  step bench 600 python3 bench.py --gpus 1 --steps 20 --warmup 5
+  step bench 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5
   cp gpurun_out/bench_full.json "$OUT/bench_full.json" 2>/dev/null
 fi
 if [ "${REHEARSE:-1}" = "1" ] && [ "${BENCH:-1}" = "1" ]; then  # the self-launched N-rank path, on one GPU

@@ -22,7 +22,7 @@ if [ -n "$VARS" ]; then
   done
 fi
 if [ -n "$BARGS" ]; then
-  timeout -k 10 400 python3 bench.py $BARGS > $OUT/bench.log 2>&1
+  timeout -k 10 400 python3 bench.py --full $BARGS > $OUT/bench.log 2>&1
   rc=$?; tail -2 $OUT/bench.log | cut -c1-300; cp gpurun_out/bench_full.json $OUT/ 2>/dev/null; [ $rc -eq 0 ] || exit 6
 fi
 echo "== session done"

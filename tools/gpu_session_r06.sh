@@ -15,7 +15,7 @@ if [ -n "$TESTS" ]; then
 fi
 if [ -n "$BARGS" ]; then
   [ "$BARGS" = "default" ] && BARGS=""
-  timeout -k 10 500 python3 bench.py $BARGS > $OUT/bench.log 2>&1
+  timeout -k 10 500 python3 bench.py --full $BARGS > $OUT/bench.log 2>&1
   rc=$?; grep '^{' $OUT/bench.log | cut -c1-400; cp gpurun_out/bench_full.json $OUT/ 2>/dev/null; [ $rc -eq 0 ] || exit 6
   grep '^{' $OUT/bench.log > $OUT/bench_line.json
 fi

@@ -1,6 +1,6 @@
 """Live PMC counters for bench.py: HBM traffic and the limiter of the very kernels it times.
 
-bench.py (N = 1, not already under a profiler) runs itself again as a child under
+bench.py --full (N = 1, not already under a profiler) runs itself again as a child under
 `rocprofv3 --pmc <group>` once per counter group (separate passes: FETCH_SIZE and WRITE_SIZE do not
 fit one pass, MI355X_MICROARCH.md "Profiling"), with `--pmc-child PLAN`: the child builds and traces
 the same workloads with nothing else launching a non-counting trace kernel, and writes the plan —
