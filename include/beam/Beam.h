@@ -238,6 +238,15 @@ class IScene {
     u32 updateGPUScene(bm_build_stats* stats) { return (u32)bm_scene_build(h_, stats); }
     // Extension: refit-only update after vertex data changed (same meshes and triangle counts).
     u32 refitGPUScene(bm_build_stats* stats = nullptr) { return (u32)bm_scene_refit(h_, stats); }
+    // Extension: ray queries over n rays in device memory (bm_scene_trace_rays; asynchronous on the
+    // context stream). traceRays: the closest hit within each ray's tmax; occluded: one byte per ray,
+    // 1 when anything lies on the segment origin -> origin + dir. flags: none defined yet (0).
+    u32 traceRays(const bm_ray* deviceRays, u32 n, bm_hit* deviceHits, u32 flags = 0) {
+        return (u32)bm_scene_trace_rays(h_, deviceRays, n, BM_RAYS_CLOSEST, flags, deviceHits);
+    }
+    u32 occluded(const bm_ray* deviceRays, u32 n, uint8_t* deviceOut, u32 flags = 0) {
+        return (u32)bm_scene_trace_rays(h_, deviceRays, n, BM_RAYS_ANY_HIT, flags, deviceOut);
+    }
     bm_scene* handle() const { return h_; }
 
    private:

@@ -271,6 +271,48 @@ int32_t bm_scene_grid_stats(bm_scene* s, uint64_t out[4]);
 int32_t bm_scene_grid_export(bm_scene* s, uint32_t* bucket_start, uint32_t* bucket_end, uint32_t* faces);
 void bm_scene_destroy(bm_scene* s);
 
+/* ---- ray queries: closest hit and any hit over a caller's batch of rays ---------------------
+ * The reference traces only its camera's rays; this is the same BVH4 traversal (ray quads) over
+ * n rays the caller wrote to device memory: ambient occlusion, bounces, picking, visibility and
+ * line-of-sight probes, anything that computes its origins and directions on the device.
+ * rays_dev and out_dev are device pointers on the context's device, 16-byte aligned. The work is
+ * enqueued on the context stream (after earlier builds and refits, before later ones) and the call
+ * returns without waiting; bm_sync waits. On a multi-device context the query runs on the root
+ * device alone. dir need not be normalised: t is in units of dir.
+ * BM_RAYS_CLOSEST: out_dev is bm_hit[n]. The closest triangle with 0 < t <= tmax (tmax = +inf:
+ *   unbounded), equal t resolved to the lowest global triangle id; u, v are its Möller-Trumbore
+ *   barycentrics. A miss writes t = +inf, u = v = 0, tri_id = BM_NO_TRIANGLE.
+ * BM_RAYS_ANY_HIT: out_dev is uint8_t[n], 1 when any triangle has 0 < t < 1 along the segment
+ *   origin -> origin + dir (the shadow rule of bm_camera_trace_shadow), else 0. tmax is ignored in
+ *   this mode.
+ * Invalid rays (a non-finite origin or direction component; closest mode: tmax NaN or <= 0) are not
+ * traced: they get the miss record, or 0.
+ * flags: none defined yet, pass 0. Rays are traced in the order given, 16 consecutive rays per
+ *   wave: neighbours that start and point alike share their node fetches.
+ * BM_ERROR_INVALID_PARAMETER: a null handle, a null pointer with n > 0, a misaligned pointer, an
+ * unknown mode or flag bit, a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT:
+ * the scene has no current build. n = 0 succeeds without a launch; over an empty built scene every
+ * ray misses. */
+typedef struct bm_ray {
+    float origin[3];
+    float tmax;
+    float dir[3];
+    uint32_t pad;
+} bm_ray; /* 32 B */
+typedef struct bm_hit {
+    float t, u, v;
+    uint32_t tri_id;
+} bm_hit; /* 16 B */
+#define BM_RAYS_CLOSEST 0u
+#define BM_RAYS_ANY_HIT 1u
+int32_t bm_scene_trace_rays(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode,
+                            uint32_t flags, void* out_dev);
+/* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle tests,
+ * out[2] hits (closest) or occluded rays (any hit); invalid rays count nothing. Results are written
+ * exactly as bm_scene_trace_rays writes them. Synchronous. */
+int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode,
+                                     uint32_t flags, void* out_dev, uint64_t out[3]);
+
 /* ---- camera: ICamera (Beam.h:65-72, Camera.cpp) ----------------------------------------- */
 int32_t bm_camera_create(bm_context* ctx, bm_camera** out);
 /* setInitialRays (Camera.cpp:43-72): same sequential ray recurrence and validation. */

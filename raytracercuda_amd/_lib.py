@@ -71,6 +71,19 @@ class BuildStats(C.Structure):
 
 SORT_LSD, SORT_MSD, SORT_MSD_SKEW, SORT_KD_RANKED = 1, 2, 3, 4
 
+
+class Ray(C.Structure):
+    """bm_ray: one ray of bm_scene_trace_rays (32 bytes)."""
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("dir", C.c_float * 3), ("pad", C.c_uint32)]
+
+
+class Hit(C.Structure):
+    """bm_hit: one closest-hit result of bm_scene_trace_rays (16 bytes)."""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("tri_id", C.c_uint32)]
+
+
+RAYS_CLOSEST, RAYS_ANY_HIT = 0, 1
+
 # bm_context_set_param keys (BM_PARAM_* in include/beam_c.h), by the names beam.Context(params=...) takes
 PARAMS = {"trace_variant": 0, "trace_sched": 1, "trace_scramble": 2, "trace_prio_after": 3, "trace_prio_level": 4,
           "trace_refill_min": 5, "cull_tiles": 6, "trace_auto_compact": 7, "trace_grid": 8, "readback_sync": 9,
@@ -125,6 +138,8 @@ SIGNATURES = {
     "bm_model_gpu_mesh": (_P, [_P, _U]),
     "bm_model_destroy": (None, [_P]),
     "bm_scene_destroy": (None, [_P]),
+    "bm_scene_trace_rays": (_I, [_P, _P, _U, _U, _U, _P]),
+    "bm_scene_trace_rays_counters": (_I, [_P, _P, _U, _U, _U, _P, _U64P]),
     "bm_camera_create": (_I, [_P, C.POINTER(_P)]),
     "bm_camera_set_initial_rays": (_I, [_P, _U, _U, _F, _F, _F, _F, _F]),
     "bm_camera_trace": (_I, [_P, _FP, _FP, _P, _P]),

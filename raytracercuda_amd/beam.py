@@ -281,6 +281,77 @@ class IScene:
             return self.last_stats
         return None
 
+    def traceRaysDevice(self, rays_ptr: int, n: int, out_ptr: int, any_hit: bool = False, counters=None,
+                        mode=None, flags=0) -> int:
+        """bm_scene_trace_rays on device pointers (n bm_ray records of 32 bytes in, n bm_hit records of
+        16 bytes or n bytes out, both 16-byte aligned); returns the error code. Asynchronous on the
+        context stream unless `counters` (a uint64[3] numpy array to fill) is given. mode overrides
+        any_hit with a raw value; flags: none defined yet."""
+        mode = (_lib.RAYS_ANY_HIT if any_hit else _lib.RAYS_CLOSEST) if mode is None else mode
+        rp, op = C.c_void_p(rays_ptr or None), C.c_void_p(out_ptr or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_trace_rays(self.h, rp, n, mode, flags, op)
+        return self.ctx.lib.bm_scene_trace_rays_counters(self.h, rp, n, mode, flags, op,
+                                                         counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def traceRays(self, origins, dirs=None, tmax=None, any_hit: bool = False, counters: bool = False):
+        """Closest hit (or, any_hit, occlusion of the segment origin -> origin + dir) of n rays of the
+        caller's own (bm_scene_trace_rays). tmax: None (unbounded), a scalar or n values; closest mode only.
+
+        numpy (n,3) float32 origins and dirs: packs, uploads, traces and waits; returns numpy arrays
+        {"t", "u", "v", "tri_id"} (a miss: t = inf, tri_id = NO_TRIANGLE) or {"occluded"}.
+        torch tensors on the context's device — origins and dirs (n,3), or one packed (n,8) float32
+        tensor (origin, tmax, dir, pad) as `origins` with dirs=None: everything stays on the device and
+        nothing waits. Returns {"hits": (n,4) float32, "t", "u", "v", "tri_id"} (views of hits; tri_id its
+        last column as int32, -1 on a miss) or {"occluded": (n,) uint8}. Make the context on torch's
+        stream (Context(stream=torch.cuda.current_stream().cuda_stream)) so the query is ordered with
+        the torch work around it.
+        counters=True adds "counters": [node records, triangle tests, hits or occluded rays] (waits)."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        on_device = isinstance(origins, torch.Tensor)
+        if on_device:
+            if dirs is None:
+                rays = origins
+                if rays.dim() != 2 or rays.shape[1] != 8:
+                    raise BeamError(ERROR_INVALID_PARAMETER, "traceRays: packed rays are (n, 8) float32")
+            else:
+                n = origins.shape[0]
+                rays = torch.zeros((n, 8), dtype=torch.float32, device=origins.device)
+                rays[:, 0:3] = origins
+                rays[:, 3] = float("inf") if tmax is None else tmax
+                rays[:, 4:7] = dirs
+            if rays.device != dev or rays.dtype != torch.float32 or not rays.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"traceRays: rays must be contiguous float32 on {dev} (the context's device)")
+        else:
+            o = _f32(origins).reshape(-1, 3)
+            packed = np.zeros((o.shape[0], 8), np.float32)
+            packed[:, 0:3] = o
+            packed[:, 3] = np.inf if tmax is None else tmax
+            packed[:, 4:7] = _f32(dirs).reshape(-1, 3)
+            rays = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = rays.shape[0]
+        out = (torch.empty((n,), dtype=torch.uint8, device=dev) if any_hit
+               else torch.empty((n, 4), dtype=torch.float32, device=dev))
+        cnt = np.zeros(3, np.uint64) if counters else None
+        self.ctx._check(self.traceRaysDevice(rays.data_ptr() if n else 0, n, out.data_ptr() if n else 0, any_hit,
+                                             cnt))
+        self._rays_keep = rays  # until the next query: the kernel may not have read them yet
+        if on_device:
+            res = ({"occluded": out} if any_hit else
+                   {"hits": out, "t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "tri_id": out.view(torch.int32)[:, 3]})
+        else:
+            self.ctx.sync()
+            h = out.cpu().numpy()
+            res = ({"occluded": h} if any_hit else
+                   {"t": h[:, 0].copy(), "u": h[:, 1].copy(), "v": h[:, 2].copy(),
+                    "tri_id": h.view(np.uint32)[:, 3].copy()})
+        if counters:
+            res["counters"] = cnt
+        return res
+
     def export(self):
         """(records[nrec, 16, 32 or 64], tris[n,12], keys[n], perm[n]) as uint32 — for parity tests.
         BVH4 records are written for every node above the leaf size, but a traversal reaches only

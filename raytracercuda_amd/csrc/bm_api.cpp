@@ -45,6 +45,7 @@ struct bm_context {
     uint32_t bvh_width = 4;     // BM_OPT_BVH2 -> 2
     void* ovf = nullptr;  // traversal-stack overflow area of the persistent trace grid
     size_t ovf_cap = 0;
+    unsigned long long* rays_counters = nullptr;  // ray queries: the counting form's three counters
     unsigned long long* tile_ctr = nullptr;  // ticket counter of the dynamic trace variants
     unsigned long long tile_base = 0;        // its value at the next launch
     // render targets with their own stream (bm_rt_set_stream): traces into them run there, ordered
@@ -588,6 +589,7 @@ void bm_context_destroy(bm_context* ctx) {
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->ovf) (void)hipFree(ctx->ovf);
     if (ctx->tile_ctr) (void)hipFree(ctx->tile_ctr);
+    if (ctx->rays_counters) (void)hipFree(ctx->rays_counters);
     if (ctx->ready) (void)hipEventDestroy(ctx->ready);
     if (ctx->post) (void)hipHostFree(ctx->post);
     delete ctx;
@@ -1443,6 +1445,42 @@ static double scene_coverage(const bm_camera* c, const bm_scene* s, const float*
     return w * h / (W * H);
 }
 
+// The traversal-stack overflow area of a persistent launch of p.variant over p.bvh_width records: sized
+// for the largest persistent grid (persistent_blocks x 256 slots; a quad kernel's slot is blockIdx.x *
+// QRAYS + ray), grow-only. rt: the render target traced into (null: a ray query, on the context stream).
+// Sets p.persistent_blocks and p.ovf_*.
+static int32_t reserve_overflow(bm_context* ctx, bm_rt* rt, hipStream_t st, bm::TraceParams& p) {
+    const uint32_t blocks = ctx->persistent_blocks ? ctx->persistent_blocks : 1024;
+    const size_t slots = (size_t)blocks * 256;
+    const size_t bytes =
+        slots * ((p.bvh_width == 8 ? bm::MAX_STACK8 : bm::MAX_STACK) - bm::trace_variant_lds(p.variant)) * 8;
+    void* ovf;
+    size_t ovf_cap;
+    if (rt && rt->stream) {  // concurrent with other streams' traces: the target's own area
+        if (bytes > rt->ovf.cap) BM_HIP(ctx, hipStreamSynchronize(st));
+        BM_HIP(ctx, rt->ovf.reserve(bytes));
+        ovf = rt->ovf.p;
+        ovf_cap = rt->ovf.cap;
+    } else {
+        if (bytes > ctx->ovf_cap) {
+            // grow-only, outside any capture: the first trace of a context allocates it
+            BM_HIP(ctx, hipStreamSynchronize(st));
+            if (ctx->ovf) (void)hipFree(ctx->ovf);
+            ctx->ovf = nullptr;
+            ctx->ovf_cap = 0;
+            BM_HIP(ctx, hipMalloc(&ctx->ovf, bytes));
+            ctx->ovf_cap = bytes;
+        }
+        ovf = ctx->ovf;
+        ovf_cap = ctx->ovf_cap;
+    }
+    p.persistent_blocks = blocks;
+    p.ovf_stride = (uint32_t)slots;
+    p.ovf_ref = reinterpret_cast<uint32_t*>(ovf);
+    p.ovf_t = reinterpret_cast<float*>(reinterpret_cast<char*>(ovf) + ovf_cap / 2);
+    return BM_ERROR_ALL_FINE;
+}
+
 static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x3, bm_scene* s, bm_rt* rt,
                           const TraceReq& rq) {
     if (!c) return BM_ERROR_INVALID_PARAMETER;
@@ -1579,34 +1617,7 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
     // wave packets run only for non-counting BVH4 primary traces; otherwise that variant takes the quad
     // (or BVH2 single-lane) kernel, whose overflow area is sized here
     if (bm::trace_variant_persistent(p.variant) || shadow || (p.variant == bm::TRACE_PACKET && !packet)) {
-        const uint32_t blocks = ctx->persistent_blocks ? ctx->persistent_blocks : 1024;
-        const size_t slots = (size_t)blocks * 256;
-        const size_t bytes =
-            slots * ((p.bvh_width == 8 ? bm::MAX_STACK8 : bm::MAX_STACK) - bm::trace_variant_lds(p.variant)) * 8;
-        void* ovf;
-        size_t ovf_cap;
-        if (rt->stream) {  // concurrent with other streams' traces: the target's own area
-            if (bytes > rt->ovf.cap) BM_HIP(ctx, hipStreamSynchronize(st));
-            BM_HIP(ctx, rt->ovf.reserve(bytes));
-            ovf = rt->ovf.p;
-            ovf_cap = rt->ovf.cap;
-        } else {
-            if (bytes > ctx->ovf_cap) {
-                // grow-only, outside any capture: the first trace of a context allocates it
-                BM_HIP(ctx, hipStreamSynchronize(st));
-                if (ctx->ovf) (void)hipFree(ctx->ovf);
-                ctx->ovf = nullptr;
-                ctx->ovf_cap = 0;
-                BM_HIP(ctx, hipMalloc(&ctx->ovf, bytes));
-                ctx->ovf_cap = bytes;
-            }
-            ovf = ctx->ovf;
-            ovf_cap = ctx->ovf_cap;
-        }
-        p.persistent_blocks = blocks;
-        p.ovf_stride = (uint32_t)slots;
-        p.ovf_ref = reinterpret_cast<uint32_t*>(ovf);
-        p.ovf_t = reinterpret_cast<float*>(reinterpret_cast<char*>(ovf) + ovf_cap / 2);
+        if (const int32_t e = reserve_overflow(ctx, rt, st, p)) return e;
     }
     if (shadow) {
         const size_t px = (size_t)rt->width * rt->height;
@@ -1676,6 +1687,63 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
     if (shadow) BM_HIP(ctx, bm::launch_shadow(p, rq.count, st));
     if (rt->stream) BM_HIP(ctx, hipEventRecord(rt->done, st));
     return BM_ERROR_ALL_FINE;
+}
+
+// ---- ray queries (bm_rays.hip) -------------------------------------------------------------------
+static int32_t rays_impl(bm_scene* s, const bm_ray* rays, uint32_t n, uint32_t mode, uint32_t flags, void* out,
+                         uint64_t* counters) {
+    if (!s) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = s->ctx;
+    if (n && (!rays || !out)) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: null ray or result pointer");
+    if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: ray and result pointers must be 16-byte aligned");
+    if (mode > BM_RAYS_ANY_HIT || flags != 0)  // no flag bits are defined
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: unknown mode or flag bits");
+    if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
+    if (s->kd || s->hash || s->width != 4)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    if (counters) counters[0] = counters[1] = counters[2] = 0;
+    if (n == 0) return BM_ERROR_ALL_FINE;
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    bm::TraceParams p{};
+    p.nodes = s->records.as<const uint4>();
+    p.tris = s->tris.as<const float4>();
+    p.num_tris = s->n;
+    p.variant = bm::TRACE_QUAD;
+    p.bvh_width = 4;
+    p.prio_after = ctx->prio_after;
+    p.prio_level = ctx->prio_level;
+    p.q_rays = reinterpret_cast<const float4*>(rays);
+    p.q_out = out;
+    p.q_n = n;
+    if (const int32_t e = reserve_overflow(ctx, nullptr, st, p)) return e;
+    if (counters) {
+        if (!ctx->rays_counters) BM_HIP(ctx, hipMalloc(&ctx->rays_counters, 3 * sizeof(unsigned long long)));
+        BM_HIP(ctx, hipMemsetAsync(ctx->rays_counters, 0, 3 * sizeof(unsigned long long), st));
+        p.counters = ctx->rays_counters;
+    }
+    BM_HIP(ctx, bm::launch_query_rays(p, mode, counters != nullptr, st));
+    if (counters) {
+        unsigned long long h[3];
+        BM_HIP(ctx, hipMemcpyAsync(h, ctx->rays_counters, sizeof(h), hipMemcpyDeviceToHost, st));
+        BM_HIP(ctx, hipStreamSynchronize(st));
+        for (int i = 0; i < 3; ++i) counters[i] = h[i];
+    }
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_trace_rays(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                            void* out_dev) {
+    return rays_impl(s, rays_dev, n, mode, flags, out_dev, nullptr);
+}
+
+int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                                     void* out_dev, uint64_t out[3]) {
+    if (!out) return BM_ERROR_INVALID_PARAMETER;
+    return rays_impl(s, rays_dev, n, mode, flags, out_dev, out);
 }
 
 static TraceReq bands_req(uint32_t band_height, uint32_t band_step, uint32_t band_first) {

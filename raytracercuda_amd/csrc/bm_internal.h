@@ -184,6 +184,11 @@ struct TraceParams {
     uint32_t* rayq_count;
     uint32_t rayq_region, rayq_tpr, rayq_regions;
     uint32_t fast_cull;  // orient is near-orthonormal: k_cull may use approximate ray setup
+    // ray queries (bm_rays.hip): q_n caller rays of two float4 each, (origin, tmax) (dir, pad); q_out one
+    // bm_hit (closest) or one byte (any hit) per ray
+    const float4* q_rays;
+    void* q_out;
+    uint32_t q_n;
 };
 
 bool trace_variant_persistent(int variant);
@@ -208,6 +213,9 @@ uint32_t trace_persistent_blocks(int variant, int device);
 hipError_t launch_trace(const TraceParams& p, bool count, hipStream_t s, uint32_t* grid);
 // Shadow pass over the queue the preceding launch_trace (with p.shadow set) filled.
 hipError_t launch_shadow(const TraceParams& p, bool count, hipStream_t s);
+// Ray query (bm_rays.hip): BM_RAYS_CLOSEST or BM_RAYS_ANY_HIT over p.q_rays on a BVH4 scene, ray quads on
+// the persistent grid with the overflow area set up as for launch_trace; count: into p.counters.
+hipError_t launch_query_rays(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
 // ---- reference mode (bm_kd.hip): the reference's kd-tree and march ---------------------------------
 struct KdBuild {
     const MeshDesc* meshes;

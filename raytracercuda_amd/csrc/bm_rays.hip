@@ -1,0 +1,107 @@
+// bm_rays.hip — ray queries: closest hit and any hit over a caller's batch of rays in device memory
+// (bm_scene_trace_rays). The traversal is the quad kernels' own (quad_closest / quad_anyhit of
+// bm_trace_dev.h, unchanged): four lanes per ray over the BVH4, the per-ray stack in LDS with the
+// global overflow area behind it, so a query returns what a camera trace of the same rays returns
+// and its COUNT build counts what oracle/beam_oracle.c counts.
+//   k_query_rays  persistent grid; a wave takes batches of 16 consecutive rays (512 contiguous bytes
+//                 of ray records), lane 4q+c works for ray 16b+q
+// The rays are traced in the order given. An ordering pass (a 30-bit origin/direction key per ray,
+// launch_sort_pairs, results scattered to the rays' own indices) was built and measured slower than
+// that on the incoherent workloads it was meant for, and is not here.
+#include "bm_trace_dev.h"
+
+namespace bm {
+namespace {
+
+constexpr int RAYS_CLOSEST = BM_RAYS_CLOSEST, RAYS_ANY_HIT = BM_RAYS_ANY_HIT;
+// Closest mode's result record: one 16-B store by the quad's first lane (16), or a dword per lane (4;
+// A/B builds, measured alike: DESIGN.md §14).
+#ifndef BM_RAYS_HIT_STORE
+#define BM_RAYS_HIT_STORE 16
+#endif
+
+__device__ __forceinline__ bool finite3(const vec3f a) {
+    return fabsf(a.x) < __builtin_inff() && fabsf(a.y) < __builtin_inff() && fabsf(a.z) < __builtin_inff();
+}
+
+// A ray record is two float4: (origin, tmax) (dir, pad). The four lanes of a quad load the same 32
+// bytes (one request per 16-B piece). An invalid ray (a non-finite origin or direction component;
+// closest mode: tmax NaN or <= 0) is finished here without traversal, so no NaN reaches a traversal
+// loop: the miss record, or 0.
+template <int MODE, bool COUNT, uint32_t PRIO>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : BM_QUAD_WAVES))) void
+k_query_rays(const TraceParams p) {
+    __shared__ uint2 s_stk[QUAD_LDS][QRAYS];
+#if BM_QUAD_LEAF_LDS
+    __shared__ float4 s_lt[QRAYS][12];
+#endif
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    const int c = lane & 3, q = lane >> 2;
+    QStack<QUAD_LDS> st;
+    st.s = s_stk;
+#if BM_QUAD_LEAF_LDS
+    st.lt = s_lt[w * 16 + q];
+#endif
+    st.ray = w * 16 + q;
+    st.g_ref = p.ovf_ref;
+    st.g_t = p.ovf_t;
+    st.slot = blockIdx.x * QRAYS + st.ray;
+    st.stride = p.ovf_stride;
+    unsigned long long cn = 0, ct = 0, ch = 0;
+    const unsigned long long none[3] = {0, 0, 0};
+    const uint32_t n = p.q_n;
+    const uint32_t nbatch = (n >> 4) + ((n & 15u) ? 1u : 0u), nwaves = gridDim.x * WAVES;
+    for (uint32_t b = blockIdx.x * WAVES + w; b < nbatch; b += nwaves) {
+        const uint32_t sidx = b * 16 + (uint32_t)q;
+        if (sidx >= n) continue;  // the last batch: whole quads only
+        const float4 r0 = p.q_rays[2 * (size_t)sidx], r1 = p.q_rays[2 * (size_t)sidx + 1];
+        const vec3f o = v3(r0.x, r0.y, r0.z), d = v3(r1.x, r1.y, r1.z);
+        bool valid = finite3(o) && finite3(d);
+        __builtin_amdgcn_s_setprio(0);
+        if (MODE == RAYS_CLOSEST) {
+            const float tmax = r0.w;
+            valid = valid && tmax > 0.0f;  // false for NaN
+            float tbest = __builtin_inff(), bu = 0.f, bv = 0.f;
+            uint32_t ibest = NO_TRI;
+            if (valid) {
+                const vec3f inv = v3(1.f / d.x, 1.f / d.y, 1.f / d.z);
+                tbest = tmax;
+                quad_closest<COUNT, PRIO>(p, st, c, o, d, inv, tbest, ibest, bu, bv, cn, ct);
+                if (ibest == NO_TRI) tbest = __builtin_inff();
+                else if (COUNT && c == 0) ++ch;
+            }
+#if BM_RAYS_HIT_STORE == 16
+            if (c == 0) reinterpret_cast<float4*>(p.q_out)[sidx] = make_float4(tbest, bu, bv, u2f(ibest));
+#else
+            reinterpret_cast<float*>(p.q_out)[4 * (size_t)sidx + c] = c == 0 ? tbest : c == 1 ? bu : c == 2 ? bv : u2f(ibest);
+#endif
+        } else {
+            bool occ = false;
+            if (valid && p.num_tris) {  // quad_anyhit starts at the root without looking at num_tris
+                occ = quad_anyhit<COUNT, PRIO>(p, st, c, o, d, cn, ct);
+                if (COUNT && c == 0) ch += occ;
+            }
+            if (c == 0) reinterpret_cast<uint8_t*>(p.q_out)[sidx] = occ ? 1 : 0;
+        }
+    }
+    flush_counters<COUNT>(p, cn, ct, ch, none);
+}
+
+template <int MODE>
+void launch_count(const TraceParams& p, bool count, hipStream_t s) {
+    if (count) launch_persistent(k_query_rays<MODE, true, 1>, p, s, nullptr);
+    else if (p.prio_after == 0) launch_persistent(k_query_rays<MODE, false, 0>, p, s, nullptr);
+    else launch_persistent(k_query_rays<MODE, false, 1>, p, s, nullptr);
+}
+
+}  // namespace
+
+hipError_t launch_query_rays(const TraceParams& p, uint32_t mode, bool count, hipStream_t s) {
+    if (p.q_n == 0) return hipSuccess;
+    if (p.bvh_width != 4 || mode > BM_RAYS_ANY_HIT) return hipErrorInvalidValue;
+    if (mode == BM_RAYS_CLOSEST) launch_count<RAYS_CLOSEST>(p, count, s);
+    else launch_count<RAYS_ANY_HIT>(p, count, s);
+    return hipGetLastError();
+}
+
+}  // namespace bm
