@@ -263,6 +263,21 @@ int32_t bm_scene_refit(bm_scene* s, bm_build_stats* stats);
 /* Reference-mode scenes: out[0] leaves holding faces, out[1] face references stored, out[2] faces
  * dropped by the 256 cap, out[3] largest leaf (before the cap). Synchronous. */
 int32_t bm_scene_kd_stats(bm_scene* s, uint64_t out[4]);
+/* Reference-mode scenes, for tests: the last build's kd-tree as the march reads it. With L = out[0] of
+ * bm_scene_kd_stats and M = *num_pairs (the (leaf, face) pairs, = the sum of leaf_count):
+ *   leaf_key[L]    31-bit root-to-leaf paths (depth 0 in the highest of the leaf-depth bits, right = 1),
+ *                  ascending
+ *   leaf_start[L], leaf_count[L]  leaf i holds faces[leaf_start[i] .. + leaf_count[i]); the count is the
+ *                  one before the 256 cap (the march tests the first 256)
+ *   faces[M]       global triangle ids, ascending within a leaf
+ *   lch, rch, first, last [L - 1]  the radix tree over the leaf keys (root = node 0): a child is an
+ *                  internal node's index, or a leaf's index with bit 31 (0x80000000) set; node i covers
+ *                  leaves first[i] .. last[i]. Nothing is written for L < 2.
+ * Any pointer may be NULL (call once with num_pairs alone to size faces). Synchronous; launches nothing.
+ * BM_ERROR_NOT_BUILT before a build, BM_ERROR_INVALID_PARAMETER on a scene of another mode. */
+int32_t bm_scene_kd_export(bm_scene* s, uint64_t* num_pairs, uint32_t* leaf_key, uint32_t* leaf_start,
+                           uint32_t* leaf_count, uint32_t* faces, uint32_t* lch, uint32_t* rch, uint32_t* first,
+                           uint32_t* last);
 /* Hashed-grid scenes: out[0] (cell, face) pairs, out[1] non-empty buckets, out[2] largest bucket,
  * out[3] faces beyond the 256 cap. Synchronous. (Hash.cu:82-89, BuildTree.cuh:21) */
 int32_t bm_scene_grid_stats(bm_scene* s, uint64_t out[4]);

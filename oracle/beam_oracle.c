@@ -445,6 +445,40 @@ void orc_kd_stats(const orc_kd* kd, uint64_t stats[8]) {
     }
 }
 
+/* The leaves that hold faces, in ascending path order: a depth-first walk, left child first. Faces are
+ * inserted at the stop depth only (kd_insert_tri), one depth for the whole tree, so a node with
+ * count > 0 is a leaf there; childless nodes above it (a triangle passed the node's box test and failed
+ * both children's) hold nothing and are passed over. */
+uint32_t orc_kd_leaves(const orc_kd* kd, uint32_t* keys, uint32_t* counts, uint32_t* faces, uint32_t* depth) {
+    struct { int32_t n; uint32_t d, path; } st[2 * KD_MAX_DEPTH];
+    int top = 0;
+    uint32_t nl = 0;
+    size_t nf = 0;
+    st[0].n = 0;
+    st[0].d = 0;
+    st[0].path = 0;
+    if (depth) *depth = 0;
+    while (top >= 0) {
+        const int32_t n = st[top].n;
+        const uint32_t d = st[top].d, path = st[top].path;
+        top--;
+        const kd_node* nd = &kd->nodes[n];
+        if (nd->count > 0) {
+            const uint32_t stored = nd->count < KD_LEAF_CAP ? nd->count : KD_LEAF_CAP;
+            if (keys) keys[nl] = path;
+            if (counts) counts[nl] = nd->count;
+            if (faces) memcpy(faces + nf, kd->groups + (size_t)nd->group * KD_LEAF_CAP, sizeof(uint32_t) * stored);
+            if (depth) *depth = d;
+            nf += stored;
+            nl++;
+        }
+        /* right pushed first: the left subtree (smaller paths) is walked before it */
+        if (nd->right >= 0) { ++top; st[top].n = nd->right; st[top].d = d + 1; st[top].path = (path << 1) | 1u; }
+        if (nd->left >= 0) { ++top; st[top].n = nd->left; st[top].d = d + 1; st[top].path = path << 1; }
+    }
+    return nl;
+}
+
 /* bmBoxRayIntersect (CudaComon.cuh:158-172) */
 static inline float kd_box_ray(const float* bmn, const float* bmx, const float* o, const float* inv) {
     float t0[3], t1[3];

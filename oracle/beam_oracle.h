@@ -61,6 +61,13 @@ orc_kd* orc_kd_build(const orc_mesh* meshes, uint32_t num_meshes, float wmin, fl
 /* stats[0]=nodes [1]=leaves [2]=face refs stored [3]=dropped (leaf cap 256) [4]=max leaf count
  * [5]=max leaf depth */
 void    orc_kd_stats(const orc_kd* kd, uint64_t stats[8]);
+/* The leaves that hold faces (count > 0, all at the tree's one leaf depth), in ascending key order.
+ * keys[i]: the root-to-leaf path, depth 0 in the highest of the leaf-depth bits, right = 1 (the low 32
+ * bits of it for a tree deeper than 32); counts[i]: faces inserted (counts past the 256 cap);
+ * faces: the stored ids of leaf 0, then of leaf 1, ...: the first min(count, 256) of each in insertion
+ * order (stats[2] entries in all); *depth: the leaf depth (0 without leaves). Any pointer may be NULL.
+ * Returns the number of leaves. Not stats[1], which also counts childless nodes above the leaf depth. */
+uint32_t orc_kd_leaves(const orc_kd* kd, uint32_t* keys, uint32_t* counts, uint32_t* faces, uint32_t* depth);
 void    orc_kd_free(orc_kd* kd);
 /* March pixels [begin,end) of a ray table. Any output pointer may be NULL. Miss: packed=0xFF00,
  * tri=0xFFFFFFFF, t=+inf. Returns 0 or 4 (a mesh without normals, where the reference would

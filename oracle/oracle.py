@@ -55,6 +55,8 @@ def load_oracle() -> C.CDLL:
         lib.orc_kd_build.argtypes = [mp, C.c_uint32, C.c_float, C.c_float]
         lib.orc_kd_build.restype = C.c_void_p
         lib.orc_kd_stats.argtypes = [C.c_void_p, u64p]
+        lib.orc_kd_leaves.argtypes = [C.c_void_p, u32p, u32p, u32p, u32p]
+        lib.orc_kd_leaves.restype = C.c_uint32
         lib.orc_kd_free.argtypes = [C.c_void_p]
         lib.orc_kd_march.argtypes = [C.c_void_p, f32p, C.c_uint32, C.c_uint32, f32p, f32p, u32p, u32p, f32p]
         lib.orc_kd_march.restype = C.c_int32
@@ -289,6 +291,23 @@ class OrcKd:
         if err:
             raise RuntimeError(f"orc_kd_march error {err}")
         return packed[begin:end], tri[begin:end], t[begin:end]
+
+    def stats(self):
+        st = np.zeros(8, np.uint64)
+        self.lib.orc_kd_stats(self.h, _p(st, C.c_uint64))
+        return st
+
+    def leaves(self):
+        """(keys, counts, faces, depth) of the leaves that hold faces, ascending by key (orc_kd_leaves).
+        faces: the leaves' stored ids back to back, min(counts[i], 256) per leaf in insertion order."""
+        n = int(self.lib.orc_kd_leaves(self.h, None, None, None, None))
+        stored = int(self.stats()[2])
+        keys, counts = np.zeros(max(1, n), np.uint32), np.zeros(max(1, n), np.uint32)
+        faces = np.zeros(max(1, stored), np.uint32)
+        depth = C.c_uint32(0)
+        self.lib.orc_kd_leaves(self.h, _p(keys, C.c_uint32), _p(counts, C.c_uint32), _p(faces, C.c_uint32),
+                               C.byref(depth))
+        return keys[:n], counts[:n], faces[:stored], int(depth.value)
 
     def counts(self, rays, eye, orient, begin=0, end=None):
         """(node pops = box tests, leaves entered, face tests) of the march over [begin, end)."""

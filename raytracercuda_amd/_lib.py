@@ -127,6 +127,7 @@ SIGNATURES = {
     "bm_scene_build": (_I, [_P, C.POINTER(BuildStats)]),
     "bm_scene_refit": (_I, [_P, C.POINTER(BuildStats)]),
     "bm_scene_kd_stats": (_I, [_P, _U64P]),
+    "bm_scene_kd_export": (_I, [_P, _U64P, _UP, _UP, _UP, _UP, _UP, _UP, _UP, _UP]),
     "bm_scene_grid_stats": (_I, [_P, _U64P]),
     "bm_scene_grid_export": (_I, [_P, _UP, _UP, _UP]),
     "bm_model_load": (_I, [C.c_char_p, _U, C.POINTER(_P)]),

@@ -253,6 +253,20 @@ class IScene:
         self.ctx._check(self.ctx.lib.bm_scene_kd_stats(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return out
 
+    def kdExport(self):
+        """Reference mode, for tests (bm_scene_kd_export): a dict of uint32 arrays — leaf_key, leaf_start,
+        leaf_count [leaves] (count before the 256 cap), faces [pairs], and the radix tree lch, rch, first,
+        last [leaves - 1] (a child with bit 31 set is a leaf index)."""
+        lib, u32 = self.ctx.lib, C.POINTER(C.c_uint32)
+        nl = int(self.kdStats()[0])
+        m = C.c_uint64(0)
+        self.ctx._check(lib.bm_scene_kd_export(self.h, C.byref(m), *([None] * 8)))
+        sizes = {"leaf_key": nl, "leaf_start": nl, "leaf_count": nl, "faces": int(m.value),
+                 "lch": max(nl - 1, 0), "rch": max(nl - 1, 0), "first": max(nl - 1, 0), "last": max(nl - 1, 0)}
+        out = {k: np.zeros(max(1, n), np.uint32) for k, n in sizes.items()}
+        self.ctx._check(lib.bm_scene_kd_export(self.h, None, *(out[k].ctypes.data_as(u32) for k in sizes)))
+        return {k: out[k][:n] for k, n in sizes.items()}
+
     def gridStats(self):
         """Hashed-grid mode: [(cell, face) pairs, non-empty buckets, largest bucket, faces beyond
         the 256 cap]."""

@@ -847,8 +847,9 @@ static int32_t kd_build(bm_context* ctx, bm_scene* s, const bm::BuildBuffers& b,
         kb.queue = reinterpret_cast<uint2*>(s->kd_queue.p);
         kb.qcount = b.bounds;  // words 0 (count) and 1 (overflow flag), zeroed by launch_gather above
         kb.qcount_zeroed = true;
-        // word 2: top-bit count, then the top-bit map (zeroed with them): the sort's ranked top digit
-        if (leaf_depth == 31 && ctx->tune.get(BM_PARAM_KD_TOP_RANK, 1) != 0) {
+        // word 2: top-bit count, then the top-bit map (zeroed with them): the sort's ranked top digit. A
+        // hand-off above depth KD_TOP_BITS has no nodes to mark the map from: the four plain passes
+        if (leaf_depth == 31 && kb.split >= (int)bm::KD_TOP_BITS && ctx->tune.get(BM_PARAM_KD_TOP_RANK, 1) != 0) {
             kb.topcount = b.bounds + 2;
             kb.topmap = b.bounds + 3;
         }
@@ -876,9 +877,10 @@ static int32_t kd_build(bm_context* ctx, bm_scene* s, const bm::BuildBuffers& b,
     // 0.03 or depth 37, BuildTree.cu:200) fires at one depth for all nodes: kd_leaf_depth.
     // Leaves therefore lie exactly at leaf_depth, and kd_split_depth keeps split below it.
     kb.reuse_queue = kb.split && kb.split < leaf_depth && qinfo[1] == 0;
-    // the ranked top digit needs every leaf below a queued node (the map holds their top bits) and at most
-    // 1,024 values present (ranks in one 10-bit digit); otherwise the four plain passes
-    const bool top_rank = kb.topmap && kb.reuse_queue && qinfo[2] <= 1024u;
+    // the ranked top digit needs the top bits of every leaf in the map (the count pass marks every node it
+    // reaches at depth split, queued or walked on, and every leaf lies below one) and at most 1,024 values
+    // present (ranks in one 10-bit digit); otherwise the four plain passes
+    const bool top_rank = kb.topmap && qinfo[2] <= 1024u;
     if (tot[1] > bm::MAX_PAIRS)
         return fail(ctx, BM_ERROR_GPU_ALLOC_FAIL, "reference mode: more than 2^31 (leaf, face) pairs");
     const uint32_t m = (uint32_t)tot[1];
@@ -1247,6 +1249,33 @@ int32_t bm_scene_kd_stats(bm_scene* s, uint64_t out[4]) {
     out[1] = stored;
     out[2] = dropped;
     out[3] = mx;
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_kd_export(bm_scene* s, uint64_t* num_pairs, uint32_t* leaf_key, uint32_t* leaf_start,
+                           uint32_t* leaf_count, uint32_t* faces, uint32_t* lch, uint32_t* rch, uint32_t* first,
+                           uint32_t* last) {
+    if (!s) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = s->ctx;
+    if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene not built");
+    if (!s->kd) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "kd export: not a reference-mode (kd) scene");
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    if (const int32_t r = kd_leaves_ready(s)) return r;
+    hipStream_t st = ctx->stream;
+    const size_t nl = 4 * (size_t)s->kd_leaves, ni = s->kd_leaves > 1 ? 4 * (size_t)(s->kd_leaves - 1) : 0;
+    if (num_pairs) *num_pairs = s->kd_pairs;
+    const std::pair<uint32_t*, const DevBuf*> leaf[] = {
+        {leaf_key, &s->kd_leaf_key}, {leaf_start, &s->kd_leaf_start}, {leaf_count, &s->kd_leaf_count}};
+    for (const auto& [dst, src] : leaf)
+        if (dst && nl) BM_HIP(ctx, hipMemcpyAsync(dst, src->p, nl, hipMemcpyDeviceToHost, st));
+    const std::pair<uint32_t*, const DevBuf*> node[] = {
+        {lch, &s->kd_lch}, {rch, &s->kd_rch}, {first, &s->kd_first}, {last, &s->kd_last}};
+    for (const auto& [dst, src] : node)
+        if (dst && ni) BM_HIP(ctx, hipMemcpyAsync(dst, src->p, ni, hipMemcpyDeviceToHost, st));
+    if (faces && s->kd_pairs)
+        BM_HIP(ctx, hipMemcpyAsync(faces, (s->kd_sorted_in_scratch ? s->kd_vals2 : s->kd_vals).p, 4 * (size_t)s->kd_pairs,
+                                   hipMemcpyDeviceToHost, st));
+    BM_HIP(ctx, hipStreamSynchronize(st));
     return BM_ERROR_ALL_FINE;
 }
 

@@ -232,7 +232,8 @@ struct KdBuild {
     uint2* queue = nullptr;      // queue_cap (triangle, path) items: the nodes reached at depth `split`
     uint32_t queue_cap = 0;
     uint32_t* qcount = nullptr;  // 2 words: queue length, overflow flag (a subtree walked on, not queued)
-    // count pass: the 2,048-bit map of the queued nodes' top 11 path bits (KD_TOPMAP_WORDS words, zeroed)
+    // count pass: the 2,048-bit map of the top 11 path bits of the nodes reached at depth `split`, queued or
+    // not (KD_TOPMAP_WORDS words, zeroed; only with split >= KD_TOP_BITS)
     // and the number of bits set (one word, zeroed) — the pair sort's ranked top digit (launch_sort_pairs)
     uint32_t* topmap = nullptr;
     uint32_t* topcount = nullptr;
@@ -247,6 +248,9 @@ struct KdBuild {
     bool* zeroed = nullptr;
     const Tuning* tune = nullptr;  // BM_PARAM_KD_GRID / KD_PAIR / KD_TB
 };
+// The pair sort's ranked top digit: path bits of depths 0-10. The count pass can mark them only from nodes
+// queued at a hand-off depth of at least this many levels, so a shallower split gets no map (kd_build).
+constexpr uint32_t KD_TOP_BITS = 11;
 // Depth at which the reference-mode build hands subtrees to other lanes (BM_PARAM_KD_SPLIT overrides; 0 = off)
 int kd_split_depth(int leaf_depth, const Tuning& t);
 #ifndef BM_KD_LEAF_CACHE

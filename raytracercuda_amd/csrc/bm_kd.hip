@@ -595,6 +595,13 @@ __device__ __forceinline__ bool enqueue(uint2* lq, uint32_t* lqn, uint32_t lcap,
     return true;
 }
 
+// Count pass: a node reached at depth `split` marks the top KD_TOP_BITS bits of its path in the workgroup's
+// map (k_kd_top's s_top) — when it goes to the global queue, or when a full queue leaves it to be walked on.
+__device__ __forceinline__ void kd_mark_top(const KdSplitArgs& a, uint32_t* s_top, uint32_t path) {
+    const uint32_t top = path >> (a.split - (int)KD_TOP_BITS);
+    atomicOr(&s_top[top >> 5], 1u << (top & 31u));
+}
+
 // The walk of k_kd_descend from node (path, depth) of triangle g. With `lq` (phase A) a node reached at
 // depth a.split is handed to the block's LDS queue when it has room (else walked on here).
 template <bool EMIT>
@@ -688,7 +695,8 @@ __device__ __forceinline__ void kd_child_tests(const float* mn, const float* mx,
 
 template <bool EMIT, bool PAIR, int TB, bool GRID>
 __device__ __forceinline__ void kd_walk(const KdSplitArgs& a, uint32_t g, const float* tv, uint32_t path, int depth,
-                                        uint2* lq, uint32_t* lqn, uint32_t lcap, uint32_t* st) {
+                                        uint2* lq, uint32_t* lqn, uint32_t lcap, uint32_t* st,
+                                        uint32_t* s_top = nullptr) {
     const bool lead = kd_lead<PAIR>();
     const bool fin = kd_finite(tv);
     constexpr uint32_t SW = TB / kd_w<PAIR>();  // stack stride: one column per walk (its lanes write the same words)
@@ -707,7 +715,10 @@ __device__ __forceinline__ void kd_walk(const KdSplitArgs& a, uint32_t g, const 
             int q = 0;
             if (lead) {
                 q = (int)enqueue(lq, lqn, lcap, g, path);
-                if (!q) *a.oflow = 1u;  // the queue then misses this subtree: the emit pass walks again
+                if (!q) {
+                    *a.oflow = 1u;  // the queue then misses this subtree: the emit pass walks again
+                    if (!EMIT && s_top) kd_mark_top(a, s_top, path);
+                }
             }
             queued = kd_from_lead<PAIR>(q) != 0;
         }
@@ -771,7 +782,8 @@ struct KdShare {
 
 template <bool EMIT, bool PAIR, bool GRID>
 __device__ __forceinline__ void kd_walk_shared(const KdSplitArgs& a, bool have, uint32_t path0, int depth0, uint2* lq,
-                                               uint32_t* lqn, uint32_t lcap, uint32_t* st, KdShare& S) {
+                                               uint32_t* lqn, uint32_t lcap, uint32_t* st, KdShare& S,
+                                               uint32_t* s_top = nullptr) {
     constexpr uint32_t W = kd_w<PAIR>();
     constexpr uint32_t SW = 64 / W;  // stack stride: one column per walk (its lanes write the same words)
     const uint32_t lane = threadIdx.x & 63;
@@ -828,7 +840,10 @@ __device__ __forceinline__ void kd_walk_shared(const KdSplitArgs& a, bool have, 
                 int q = 0;
                 if (lead) {
                     q = (int)enqueue(lq, lqn, lcap, g, path);
-                    if (!q) *a.oflow = 1u;
+                    if (!q) {
+                        *a.oflow = 1u;
+                        if (!EMIT && s_top) kd_mark_top(a, s_top, path);
+                    }
                 }
                 queued = kd_from_lead<PAIR>(q) != 0;
             }
@@ -890,7 +905,6 @@ __device__ __forceinline__ void kd_walk_shared(const KdSplitArgs& a, bool have, 
     }
 }
 
-constexpr uint32_t KD_TOP_BITS = 11;  // the pair sort's ranked top digit: path bits of depths 0-10
 constexpr uint32_t KD_LQ_CAP = 4 * BLOCK;  // LDS queue items per workgroup of BLOCK lanes (4 per lane)
 constexpr int KD_SPLIT_ABOVE_LEAF = 6;     // default split depth = leaf depth - 6 (cells 4x the leaf's per axis)
 
@@ -936,6 +950,7 @@ __global__ __launch_bounds__(TB) void k_kd_top(const MeshDesc* __restrict__ mesh
     // queue to the global one, the later rounds walk on the items the global queue had no room for.
     uint32_t wg = g, wpath = 0, i = 0, nq = 0;
     int wdepth = 0;
+    uint32_t* const mark = (!EMIT && a.topmap) ? s_top : nullptr;
     if constexpr (TB == 64 && BM_KD_SHARE) {  // round 0 with shared work: every lane of the wave takes part
         float tv[9];
         if (walk) load_tri(meshes, nm, g, tv);
@@ -946,7 +961,7 @@ __global__ __launch_bounds__(TB) void k_kd_top(const MeshDesc* __restrict__ mesh
         }
         __syncthreads();
         BDIAG_MARK(0);
-        kd_walk_shared<EMIT, PAIR, GRID>(a, walk, 0u, 0, lq, &lqn, lcap, stk + threadIdx.x / W, S);
+        kd_walk_shared<EMIT, PAIR, GRID>(a, walk, 0u, 0, lq, &lqn, lcap, stk + threadIdx.x / W, S, mark);
         BDIAG_MARK(1);
         walk = false;
     }
@@ -956,7 +971,7 @@ __global__ __launch_bounds__(TB) void k_kd_top(const MeshDesc* __restrict__ mesh
             load_tri(meshes, nm, wg, tv);
             BDIAG_MARK(first ? 0 : 2);
             kd_walk<EMIT, PAIR, TB, GRID>(a, wg, tv, wpath, wdepth, first ? lq : nullptr, &lqn, lcap,
-                                          stk + threadIdx.x / W);
+                                          stk + threadIdx.x / W, mark);
             BDIAG_MARK(first ? 1 : 3);
         }
         if (first) {
@@ -970,14 +985,9 @@ __global__ __launch_bounds__(TB) void k_kd_top(const MeshDesc* __restrict__ mesh
         for (; i < nq; i += TB / W) {  // the next queued item: to the global queue, or walked here
             const uint2 it = lq[i];
             const uint32_t j = gbase + i;
+            if (lead && mark) kd_mark_top(a, mark, it.y);  // whether the global queue takes it or not
             if (j < a.cap) {
-                if (lead) {
-                    a.queue[j] = it;
-                    if (!EMIT && a.topmap) {
-                        const uint32_t top = it.y >> (a.split - (int)KD_TOP_BITS);
-                        atomicOr(&s_top[top >> 5], 1u << (top & 31u));
-                    }
-                }
+                if (lead) a.queue[j] = it;
             } else {
                 if (lead) *a.oflow = 1u;
                 wg = it.x;

@@ -4,8 +4,9 @@ Bar: every pixel — the early-out pixels included, where the reference returns 
 the closest hit — equals the reference framebuffer: packed colour and triangle id bit-exact, t
 bit-exact (within 1e-5 is the contract), against the golden frames of the kd restatement
 (tests/golden/views, pinned to the SURVEY §8(c) known answers) and against the oracle's kd march on
-views no fixture covers. The tree's content is checked through its statistics (face references
-stored, faces dropped by the 256-face cap, largest leaf) against orc_kd_stats.
+views no fixture covers. The tree's statistics (face references stored, faces dropped by the 256-face
+cap, largest leaf) are compared with orc_kd_stats here; the tree itself — every leaf's key, count and
+faces, and the radix tree over the leaves — is compared with the oracle's in test_gpu_kd_export.py.
 """
 import numpy as np
 import pytest
@@ -98,10 +99,10 @@ def test_reference_mode_split_descent_queue_overflow(kctx, oracle, caps):
     assert (tri != 0xFFFFFFFF).sum() > 0
 
 
-@pytest.mark.parametrize("variant", [2, 1])
+@pytest.mark.parametrize("variant", [2, 1, 0])
 def test_reference_mode_march_variants(oracle, variant):
-    """The one-box march steps (BM_PARAM_KD_MARCH 2) and the lane-per-ray leaves (1) give the kd
-    oracle's frames as the default (3: child-box steps) does — a silhouette view with grazing rays and
+    """The one-box march steps (BM_PARAM_KD_MARCH 2) and the lane-per-ray leaves (1; 0: in 256-lane
+    workgroups of 16 x 16 pixels) give the kd oracle's frames as the default (3: child-box steps) does — a silhouette view with grazing rays and
     a view whose rays have an exactly zero direction component (chain replay lanes)."""
     ctx = beam.Context(device=0, reference_kd=True, params={"kd_march": variant})
     try:
