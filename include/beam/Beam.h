@@ -247,6 +247,11 @@ class IScene {
     u32 occluded(const bm_ray* deviceRays, u32 n, uint8_t* deviceOut, u32 flags = 0) {
         return (u32)bm_scene_trace_rays(h_, deviceRays, n, BM_RAYS_ANY_HIT, flags, deviceOut);
     }
+    // Extension: the meshes' vertex slots interpolated at n hit records in device memory, up to
+    // BM_ATTR_MAX_REQS requests per call (bm_scene_hit_attributes; asynchronous on the context stream).
+    u32 hitAttributes(const bm_hit* deviceHits, u32 n, const bm_attr_req* reqs, u32 numReqs) {
+        return (u32)bm_scene_hit_attributes(h_, deviceHits, n, reqs, numReqs);
+    }
     bm_scene* handle() const { return h_; }
 
    private:

@@ -328,6 +328,56 @@ int32_t bm_scene_trace_rays(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uin
 int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode,
                                      uint32_t flags, void* out_dev, uint64_t out[3]);
 
+/* ---- hit attributes: the meshes' vertex slots interpolated at ray-query hits ------------------
+ * The reference's bmFaceInterpolate<T>(face, u, v, meshData, dataIdx) (CudaComon.cuh:253-266) over n
+ * bm_hit records in device memory (as bm_scene_trace_rays writes them, or made by the caller): what a
+ * caller needs to shade or to start the next ray from, without mirroring the meshes itself.
+ * For hit i with tri_id = g: the scene mesh m and its face f with tri_offset[m] <= g < tri_offset[m] +
+ * num_tris[m] (global ids as bm_scene_build defines them), the indices idx[3f .. 3f+2] of mesh m, the
+ * vertices a0, a1, a2 of the requested slot there, and per component, in float32 without contraction,
+ *     w = 1.f - (u + v);  out = (a0 * w + a1 * u) + a2 * v
+ * (the trace's own normal interpolation). BM_ATTR_NORMALIZE (3-component requests) multiplies every
+ * component by 1.f / sqrtf((x*x + y*y) + z*z).
+ * Pseudo-slots: BM_ATTR_GEOM_NORMAL: with e1 = v1 - v0, e2 = v2 - v0 of the position slot,
+ *   (e1.y*e2.z - e2.y*e1.z, e1.z*e2.x - e2.z*e1.x, e1.x*e2.y - e2.x*e1.y), normalised on request;
+ *   BM_ATTR_MESH_FACE: the uint32 pair {m, f}.
+ * Misses: a record whose tri_id is BM_NO_TRIANGLE, or >= the built triangle count, is not looked up: its
+ *   rows are zeros, {0xFFFFFFFF, 0xFFFFFFFF} for BM_ATTR_MESH_FACE. Only tri_id ever indexes memory; u and
+ *   v are used as given (a non-finite u or v propagates arithmetically).
+ * Mixed scenes: every mesh that has the requested slot must have `components` components there and at
+ *   least one mesh of the scene must have it, else BM_ERROR_INVALID_FORMAT (a scene without meshes has
+ *   only misses and accepts any slot); hits on a mesh without the slot get zero rows (NORMALIZE or not).
+ * The values read are the meshes' device buffers when the kernel runs: a bm_mesh_set_vertex_data after
+ *   the build is seen without a rebuild (positions and normals after a bm_scene_refit likewise). The
+ *   mesh set and the triangle counts must be those of the last build or refit (bm_scene_refit's own
+ *   comparison), else BM_ERROR_NOT_BUILT; every mesh's largest index must be below its vertex count at
+ *   call time, else BM_ERROR_INVALID_PARAMETER.
+ * 1..BM_ATTR_MAX_REQS requests are served by one launch that finds the mesh and loads the indices once
+ *   per hit; the result is bit-identical to one call per request. hits_dev and every out_dev are device
+ *   pointers on the context's device, 16-byte aligned; out_dev receives n rows of `components` 4-byte
+ *   words, tightly packed. The work is enqueued on the context stream (after earlier builds and ray
+ *   queries) and the call returns without waiting; repeated calls over unchanged meshes do not
+ *   synchronise with the device. On a multi-device context it runs on the root device alone.
+ * BM_ERROR_INVALID_PARAMETER: a null handle or request array, null hits_dev or out_dev with n > 0, a
+ *   misaligned hits_dev or out_dev, num_reqs 0 or > BM_ATTR_MAX_REQS, an unknown slot or flag bit,
+ *   components outside 1..4 (BM_ATTR_GEOM_NORMAL: 3, BM_ATTR_MESH_FACE: 2), BM_ATTR_NORMALIZE on a
+ *   request that is not 3-component or is BM_ATTR_MESH_FACE, non-zero pad, a scene of a reference-mode,
+ *   BVH2 or BVH8 context (bm_hit records only come from BVH4 scenes; the kernel does not read the BVH).
+ * BM_ERROR_NOT_BUILT: no current build. n = 0 succeeds without a launch. */
+#define BM_ATTR_GEOM_NORMAL 16u /* pseudo-slot: cross(v1-v0, v2-v0) of the position slot, 3 floats, unnormalised */
+#define BM_ATTR_MESH_FACE 17u   /* pseudo-slot: uint32 {scene mesh index, face index within it}, 2 words */
+#define BM_ATTR_NORMALIZE 1u    /* flags: 3-component requests only; v * (1.f / sqrtf(dot(v,v))) */
+#define BM_ATTR_MAX_REQS 4u
+typedef struct bm_attr_req {
+    uint32_t slot;       /* BM_VERTEX_DATA_* or a BM_ATTR_* pseudo-slot */
+    uint32_t components; /* floats per output row: 1..4 (GEOM_NORMAL 3, MESH_FACE 2) */
+    uint32_t flags;      /* BM_ATTR_* bits */
+    uint32_t pad;        /* 0 */
+    void* out_dev;       /* n rows of `components` 4-byte words, tightly packed; 16-byte aligned base */
+} bm_attr_req;           /* 24 B */
+int32_t bm_scene_hit_attributes(bm_scene* s, const bm_hit* hits_dev, uint32_t n, const bm_attr_req* reqs,
+                                uint32_t num_reqs);
+
 /* ---- camera: ICamera (Beam.h:65-72, Camera.cpp) ----------------------------------------- */
 int32_t bm_camera_create(bm_context* ctx, bm_camera** out);
 /* setInitialRays (Camera.cpp:43-72): same sequential ray recurrence and validation. */

@@ -27,6 +27,14 @@ ERROR_NOT_BUILT = 10
 
 VERTEX_DATA_POSITION = 0
 VERTEX_DATA_NORMAL = 1
+VERTEX_DATA_UV1 = 2
+VERTEX_DATA_UV2 = 3
+VERTEX_DATA_TANGENT = 4
+VERTEX_DATA_BITANGENT = 5
+VERTEX_DATA_EXTRA1 = 6
+VERTEX_DATA_EXTRA2 = 7
+VERTEX_DATA_EXTRA3 = 8
+VERTEX_DATA_EXTRA4 = 9
 VERTEX_DATA_COUNT = 10
 OPT_NULL_STREAM = 1
 OPT_SHADOW_QUEUE = 2
@@ -83,6 +91,17 @@ class Hit(C.Structure):
 
 
 RAYS_CLOSEST, RAYS_ANY_HIT = 0, 1
+
+
+class AttrReq(C.Structure):
+    """bm_attr_req: one request of bm_scene_hit_attributes (24 bytes)."""
+    _fields_ = [("slot", C.c_uint32), ("components", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32),
+                ("out_dev", C.c_void_p)]
+
+
+ATTR_GEOM_NORMAL, ATTR_MESH_FACE = 16, 17  # pseudo-slots
+ATTR_NORMALIZE = 1                         # flag
+ATTR_MAX_REQS = 4
 
 # bm_context_set_param keys (BM_PARAM_* in include/beam_c.h), by the names beam.Context(params=...) takes
 PARAMS = {"trace_variant": 0, "trace_sched": 1, "trace_scramble": 2, "trace_prio_after": 3, "trace_prio_level": 4,
@@ -141,6 +160,7 @@ SIGNATURES = {
     "bm_scene_destroy": (None, [_P]),
     "bm_scene_trace_rays": (_I, [_P, _P, _U, _U, _U, _P]),
     "bm_scene_trace_rays_counters": (_I, [_P, _P, _U, _U, _U, _P, _U64P]),
+    "bm_scene_hit_attributes": (_I, [_P, _P, _U, C.POINTER(AttrReq), _U]),
     "bm_camera_create": (_I, [_P, C.POINTER(_P)]),
     "bm_camera_set_initial_rays": (_I, [_P, _U, _U, _F, _F, _F, _F, _F]),
     "bm_camera_trace": (_I, [_P, _FP, _FP, _P, _P]),

@@ -26,7 +26,10 @@ from ._lib import (ERROR_ALL_FINE, ERROR_DEVICE, ERROR_GPU_ALLOC_FAIL, ERROR_INV
                    ERROR_INVALID_PARAMETER, ERROR_LOCK_FIRST, ERROR_NO_RENDER_TARGET, ERROR_NO_VERTICES,
                    ERROR_NOT_BUILT, ERROR_RT_CAM_MISMATCH, ERROR_UNLOCK_FIRST, MISS_PACKED, NO_TRIANGLE,
                    VERTEX_DATA_COUNT, VERTEX_DATA_NORMAL, VERTEX_DATA_POSITION, BeamError, BuildStats, Options,
-                   SORT_LSD, SORT_MSD, SORT_MSD_SKEW, SORT_KD_RANKED)
+                   SORT_LSD, SORT_MSD, SORT_MSD_SKEW, SORT_KD_RANKED,
+                   VERTEX_DATA_UV1, VERTEX_DATA_UV2, VERTEX_DATA_TANGENT, VERTEX_DATA_BITANGENT, VERTEX_DATA_EXTRA1,
+                   VERTEX_DATA_EXTRA2, VERTEX_DATA_EXTRA3, VERTEX_DATA_EXTRA4,
+                   ATTR_GEOM_NORMAL, ATTR_MESH_FACE, ATTR_NORMALIZE, ATTR_MAX_REQS)
 
 
 def _f32(a):
@@ -366,6 +369,55 @@ class IScene:
             res["counters"] = cnt
         return res
 
+    def hitAttributesDevice(self, hits_ptr: int, n: int, requests) -> int:
+        """bm_scene_hit_attributes on device pointers: n bm_hit records of 16 bytes in, and per request
+        (slot, components, flags, out_ptr[, pad]) n rows of `components` 4-byte words out, every pointer
+        16-byte aligned; returns the error code. Asynchronous on the context stream."""
+        requests = list(requests)
+        arr = (_lib.AttrReq * max(len(requests), 1))()
+        for a, r in zip(arr, requests):
+            a.slot, a.components, a.flags, a.out_dev = r[0], r[1], r[2], r[3] or None
+            a.pad = r[4] if len(r) > 4 else 0
+        return self.ctx.lib.bm_scene_hit_attributes(self.h, C.c_void_p(hits_ptr or None), n, arr, len(requests))
+
+    def hitAttributes(self, hits, requests):
+        """The meshes' vertex slots interpolated at hit records (bm_scene_hit_attributes): the shading normal,
+        texture coordinate, tangent frame or position a caller needs to shade a hit or start the next ray.
+
+        hits: the (n,4) float32 tensor traceRays returns under "hits" (t, u, v, tri_id bits), or a numpy
+        array of the same layout. requests: up to ATTR_MAX_REQS tuples (slot, components[, flags]) — a
+        VERTEX_DATA_* slot, or ATTR_GEOM_NORMAL (3 components) or ATTR_MESH_FACE (2); flags ATTR_NORMALIZE
+        for 3-component rows. Returns one (n, components) array per request: float32, except ATTR_MESH_FACE
+        which is int32 (scene mesh index, face index), -1 on a miss; every other row of a miss is zero.
+        torch tensors stay on the device and nothing waits (make the context on torch's stream, as for
+        traceRays); numpy in gives numpy out and waits."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        on_device = isinstance(hits, torch.Tensor)
+        if on_device:
+            h = hits
+            if h.dim() != 2 or h.shape[1] != 4 or h.device != dev or h.dtype != torch.float32 or not h.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"hitAttributes: hits must be contiguous (n, 4) float32 on {dev} (the context's device)")
+        else:
+            a = np.ascontiguousarray(hits)
+            if a.dtype != np.float32:
+                a = a.view(np.float32) if a.dtype.itemsize == 4 else a.astype(np.float32)
+            h = torch.from_numpy(a.reshape(-1, 4)).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = h.shape[0]
+        reqs = [tuple(r) + (0,) * (3 - len(r)) for r in requests]
+        outs = [torch.empty((n, int(r[1])), dtype=torch.int32 if r[0] == ATTR_MESH_FACE else torch.float32, device=dev)
+                for r in reqs]
+        self.ctx._check(self.hitAttributesDevice(h.data_ptr() if n else 0, n,
+                                                 [(r[0], r[1], r[2], o.data_ptr() if n else 0)
+                                                  for r, o in zip(reqs, outs)]))
+        self._attrs_keep = h  # until the next call: the kernel may not have read them yet
+        if on_device:
+            return outs
+        self.ctx.sync()
+        return [o.cpu().numpy() for o in outs]
+
     def export(self):
         """(records[nrec, 16, 32 or 64], tris[n,12], keys[n], perm[n]) as uint32 — for parity tests.
         BVH4 records are written for every node above the leaf size, but a traversal reaches only
@@ -678,7 +730,8 @@ def reachable_records(records: np.ndarray) -> np.ndarray:
 
 
 def upload_meshes(ctx: Context, scene: IScene, meshes):
-    """Create one IMesh per mesh dict {pos, nrm, idx} (Model::load order) and add it to scene."""
+    """Create one IMesh per mesh dict {pos, nrm, idx} (Model::load order) and add it to scene. An optional
+    "slots": {slot_id: array (V, components)} uploads further vertex slots (hitAttributes reads them)."""
     out = []
     for m in meshes:
         mesh = IMesh.create(ctx)
@@ -689,6 +742,9 @@ def upload_meshes(ctx: Context, scene: IScene, meshes):
         if m.get("nrm") is not None:
             nrm = _f32(m["nrm"]).reshape(-1, 3)
             ctx._check(mesh.setVertexData(nrm, nrm.shape[0], 3, VERTEX_DATA_NORMAL))
+        for slot, data in (m.get("slots") or {}).items():
+            data = _f32(data).reshape(pos.shape[0], -1)
+            ctx._check(mesh.setVertexData(data, data.shape[0], data.shape[1], int(slot)))
         scene.addMesh(mesh)
         out.append(mesh)
     return out

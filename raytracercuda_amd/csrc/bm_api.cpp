@@ -177,6 +177,13 @@ struct bm_scene {
     bool kd_cnodes_valid = false;      // the last build wrote the child-box records (BM_PARAM_KD_MARCH 3)
     uint32_t scan_epoch = 0;           // launch_exclusive_scan's call epoch on kd_sums (no zero fill per call)
     uint32_t num_meshes = 0;           // mesh-table entries of the last build
+    // hit attributes (bm_attrs.hip): the per-mesh slot table (AttrMesh entries, then their offsets packed),
+    // uploaded through pinned staging only when it differs from attr_host, the last image uploaded
+    DevBuf attr_table;
+    std::vector<unsigned char> attr_host;
+    unsigned char* attr_staging = nullptr;
+    size_t attr_staging_cap = 0;
+    hipEvent_t attr_done = nullptr;    // the last upload has left attr_staging
 };
 
 struct bm_camera {
@@ -1348,8 +1355,10 @@ void bm_scene_destroy(bm_scene* s) {
                       &s->kd_leaf_of, &s->kd_leaf_key, &s->kd_leaf_start, &s->kd_leaf_count,
                       &s->kd_lch, &s->kd_rch, &s->kd_first, &s->kd_last, &s->kd_pleaf, &s->kd_pint, &s->kd_nodes, &s->kd_cnodes,
                       &s->kd_leafrec, &s->kd_ftris, &s->kd_node_key, &s->kd_ubox, &s->kd_cache,
-                      &s->kd_queue, &s->kd_fill, &s->hash_bstart, &s->hash_bend})
+                      &s->kd_queue, &s->kd_fill, &s->hash_bstart, &s->hash_bend, &s->attr_table})
         b->release();
+    if (s->attr_staging) (void)hipHostFree(s->attr_staging);
+    if (s->attr_done) (void)hipEventDestroy(s->attr_done);
     if (s->staging) (void)hipHostFree(s->staging);
     if (s->hbounds) (void)hipHostFree(s->hbounds);
     if (s->kd_post) (void)hipHostFree(s->kd_post);
@@ -1773,6 +1782,115 @@ int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32
                                      void* out_dev, uint64_t out[3]) {
     if (!out) return BM_ERROR_INVALID_PARAMETER;
     return rays_impl(s, rays_dev, n, mode, flags, out_dev, out);
+}
+
+// ---- hit attributes (bm_attrs.hip) ---------------------------------------------------------------
+int32_t bm_scene_hit_attributes(bm_scene* s, const bm_hit* hits_dev, uint32_t n, const bm_attr_req* reqs,
+                                uint32_t num_reqs) {
+    if (!s) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = s->ctx;
+    if (!reqs || num_reqs == 0 || num_reqs > BM_ATTR_MAX_REQS)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: 1..4 requests");
+    if (n && !hits_dev) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: null hit records");
+    if (reinterpret_cast<uintptr_t>(hits_dev) & 15u)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: hit records must be 16-byte aligned");
+    bm::AttrParams p{};
+    for (uint32_t r = 0; r < num_reqs; ++r) {
+        const bm_attr_req& q = reqs[r];
+        bm::AttrReq& d = p.req[r];
+        if (q.slot < BM_VERTEX_DATA_COUNT) d.kind = bm::ATTR_SLOT;
+        else if (q.slot == BM_ATTR_GEOM_NORMAL) d.kind = bm::ATTR_GEOM_NORMAL;
+        else if (q.slot == BM_ATTR_MESH_FACE) d.kind = bm::ATTR_MESH_FACE;
+        else return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: unknown slot");
+        if (q.flags & ~BM_ATTR_NORMALIZE) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: unknown flag bits");
+        if (q.components < 1 || q.components > 4 || (d.kind == bm::ATTR_GEOM_NORMAL && q.components != 3) ||
+            (d.kind == bm::ATTR_MESH_FACE && q.components != 2))
+            return fail(ctx, BM_ERROR_INVALID_PARAMETER,
+                        "hit_attributes: components 1..4 (BM_ATTR_GEOM_NORMAL 3, BM_ATTR_MESH_FACE 2)");
+        if ((q.flags & BM_ATTR_NORMALIZE) && (q.components != 3 || d.kind == bm::ATTR_MESH_FACE))
+            return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: BM_ATTR_NORMALIZE needs a 3-component request");
+        if (q.pad != 0) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: pad must be 0");
+        if (n && !q.out_dev) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: null result pointer");
+        if (reinterpret_cast<uintptr_t>(q.out_dev) & 15u)
+            return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: result pointers must be 16-byte aligned");
+        d.out = q.out_dev;
+        d.slot = d.kind == bm::ATTR_SLOT ? q.slot : 0u;
+        d.comps = q.components;
+        d.normalize = q.flags & BM_ATTR_NORMALIZE;
+    }
+    if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
+    if (s->kd || s->hash || s->width != 4)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    // the table below describes the meshes as they are now: they must still be the build's
+    bool same = s->built_with.size() == s->meshes.size();
+    for (size_t i = 0; same && i < s->meshes.size(); ++i)
+        same = s->built_with[i].first == s->meshes[i] && s->built_with[i].second == s->meshes[i]->num_indices / 3;
+    if (!same)
+        return fail(ctx, BM_ERROR_NOT_BUILT,
+                    "hit_attributes needs the meshes and triangle counts of the last build (call updateGPUScene)");
+    const size_t nm = s->meshes.size();
+    std::vector<unsigned char> image((sizeof(bm::AttrMesh) + sizeof(uint32_t)) * nm);
+    bm::AttrMesh* tab = reinterpret_cast<bm::AttrMesh*>(image.data());
+    uint32_t* offs = reinterpret_cast<uint32_t*>(image.data() + sizeof(bm::AttrMesh) * nm);
+    uint32_t have[BM_VERTEX_DATA_COUNT] = {};  // meshes carrying each slot
+    uint32_t off = 0;
+    for (size_t i = 0; i < nm; ++i) {
+        const bm_mesh* m = s->meshes[i];
+        if (m->num_indices && (!m->idx.p || m->max_index >= m->num_vertices))
+            return fail(ctx, BM_ERROR_INVALID_PARAMETER, "index out of range of the mesh's vertices");
+        bm::AttrMesh d{};
+        d.idx = m->idx.as<const uint32_t>();
+        d.tri_offset = off;
+        d.num_tris = m->num_indices / 3;
+        for (uint32_t k = 0; k < BM_VERTEX_DATA_COUNT; ++k) {
+            const bool has = m->slot[k].p && m->slot_comp[k];
+            d.slot[k] = has ? m->slot[k].as<const float>() : nullptr;
+            have[k] += has;
+        }
+        for (uint32_t r = 0; r < num_reqs; ++r)
+            if (p.req[r].kind == bm::ATTR_SLOT && d.slot[p.req[r].slot] && m->slot_comp[p.req[r].slot] != p.req[r].comps)
+                return fail(ctx, BM_ERROR_INVALID_FORMAT,
+                            "hit_attributes: a mesh has the slot with another number of components");
+        std::memcpy(tab + i, &d, sizeof(d));
+        offs[i] = off;
+        off += d.num_tris;
+    }
+    for (uint32_t r = 0; r < num_reqs; ++r)
+        if (p.req[r].kind == bm::ATTR_SLOT && nm && !have[p.req[r].slot])
+            return fail(ctx, BM_ERROR_INVALID_FORMAT, "hit_attributes: no mesh of the scene has the slot");
+    if (off != s->n) return fail(ctx, BM_ERROR_NOT_BUILT, "hit_attributes: triangle count differs from the build's");
+    if (n == 0) return BM_ERROR_ALL_FINE;
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    if (nm && image != s->attr_host) {
+        s->attr_host.clear();  // unknown until the new image is on its way
+        if (!s->attr_done) BM_HIP(ctx, hipEventCreateWithFlags(&s->attr_done, hipEventDisableTiming));
+        else BM_HIP(ctx, hipEventSynchronize(s->attr_done));  // the previous upload still reads the staging area
+        if (image.size() > s->attr_staging_cap) {
+            if (s->attr_staging) (void)hipHostFree(s->attr_staging);
+            s->attr_staging = nullptr;
+            s->attr_staging_cap = 0;
+            BM_HIP(ctx, hipHostMalloc((void**)&s->attr_staging, image.size(), hipHostMallocDefault));
+            s->attr_staging_cap = image.size();
+        }
+        GrowGuard grow{ctx};  // an earlier query still queued may read the old table
+        BM_HIP(ctx, grow.reserve(s->attr_table, image.size()));
+        std::memcpy(s->attr_staging, image.data(), image.size());
+        BM_HIP(ctx, hipMemcpyAsync(s->attr_table.p, s->attr_staging, image.size(), hipMemcpyHostToDevice, st));
+        BM_HIP(ctx, hipEventRecord(s->attr_done, st));
+        s->attr_host = std::move(image);
+    }
+    p.hits = reinterpret_cast<const float4*>(hits_dev);
+    p.n = n;
+    p.num_tris = s->n;
+    p.num_meshes = (uint32_t)nm;
+    p.meshes = s->attr_table.as<const bm::AttrMesh>();
+    p.offsets = reinterpret_cast<const uint32_t*>(s->attr_table.as<const unsigned char>() + sizeof(bm::AttrMesh) * nm);
+    p.num_reqs = num_reqs;
+    BM_HIP(ctx, bm::launch_hit_attrs(p, st));
+    return BM_ERROR_ALL_FINE;
 }
 
 static TraceReq bands_req(uint32_t band_height, uint32_t band_step, uint32_t band_first) {

@@ -216,6 +216,36 @@ hipError_t launch_shadow(const TraceParams& p, bool count, hipStream_t s);
 // Ray query (bm_rays.hip): BM_RAYS_CLOSEST or BM_RAYS_ANY_HIT over p.q_rays on a BVH4 scene, ray quads on
 // the persistent grid with the overflow area set up as for launch_trace; count: into p.counters.
 hipError_t launch_query_rays(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
+// ---- hit attributes (bm_attrs.hip): vertex slots interpolated at the hits of a ray query ------------
+// One entry per scene mesh, in scene order: every slot's device buffer (null: the mesh has none), so the
+// table depends on the meshes alone and not on what a call requests.
+struct AttrMesh {
+    const uint32_t* idx;  // 3 per face
+    uint32_t tri_offset;  // first global triangle id of this mesh
+    uint32_t num_tris;
+    const float* slot[BM_VERTEX_DATA_COUNT];
+};  // 96 B
+static_assert(sizeof(AttrMesh) == 96, "AttrMesh is uploaded as a byte image: no padding");
+enum AttrKind : uint32_t { ATTR_SLOT = 0, ATTR_GEOM_NORMAL = 1, ATTR_MESH_FACE = 2 };
+struct AttrReq {
+    void* out;       // n rows of comps words
+    uint32_t kind;   // AttrKind
+    uint32_t slot;   // ATTR_SLOT: the vertex slot read
+    uint32_t comps;  // 1..4
+    uint32_t normalize;
+};
+struct AttrParams {
+    const float4* hits;       // n bm_hit records
+    uint32_t n;
+    uint32_t num_tris;        // the build's triangle count: ids at or above it are misses
+    uint32_t num_meshes;
+    const AttrMesh* meshes;   // num_meshes entries
+    const uint32_t* offsets;  // their tri_offset again, packed for the search
+    uint32_t num_reqs;        // 1..BM_ATTR_MAX_REQS
+    AttrReq req[BM_ATTR_MAX_REQS];
+};
+hipError_t launch_hit_attrs(const AttrParams& p, hipStream_t s);
+
 // ---- reference mode (bm_kd.hip): the reference's kd-tree and march ---------------------------------
 struct KdBuild {
     const MeshDesc* meshes;
