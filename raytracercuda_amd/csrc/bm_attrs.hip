@@ -1,6 +1,6 @@
 // bm_attrs.hip — hit attributes: the meshes' vertex slots interpolated at the hits of a ray query
 // (bm_scene_hit_attributes). The reference's bmFaceInterpolate<T> (CudaComon.cuh:253-266) for any slot,
-// in the operation order of shade_normals (bm_trace_dev.h): w = 1 - (u + v); (a0*w + a1*u) + a2*v.
+// in the operation order of shade_normals (bm_trace_dev.h, shared by every trace kernel): w = 1 - (u + v); (a0*w + a1*u) + a2*v.
 //   k_hit_attrs<NREQ>  one lane per bm_hit record: a 16-B load of the record, the mesh by binary search
 //                      over the packed tri_offset array (skipped for a one-mesh scene), the face's three
 //                      indices, then per request three vertex reads and one row store. The mesh and the

@@ -1,6 +1,6 @@
 // bm_rays.hip — ray queries: closest hit and any hit over a caller's batch of rays in device memory
 // (bm_scene_trace_rays). The traversal is the quad kernels' own (quad_closest / quad_anyhit of
-// bm_trace_dev.h, unchanged): four lanes per ray over the BVH4, the per-ray stack in LDS with the
+// bm_trace_quad.h, unchanged): four lanes per ray over the BVH4, the per-ray stack in LDS with the
 // global overflow area behind it, so a query returns what a camera trace of the same rays returns
 // and its COUNT build counts what oracle/beam_oracle.c counts.
 //   k_query_rays  persistent grid; a wave takes batches of 16 consecutive rays (512 contiguous bytes
@@ -8,17 +8,12 @@
 // The rays are traced in the order given. An ordering pass (a 30-bit origin/direction key per ray,
 // launch_sort_pairs, results scattered to the rays' own indices) was built and measured slower than
 // that on the incoherent workloads it was meant for, and is not here.
-#include "bm_trace_dev.h"
+#include "bm_trace_quad.h"
 
 namespace bm {
 namespace {
 
 constexpr int RAYS_CLOSEST = BM_RAYS_CLOSEST, RAYS_ANY_HIT = BM_RAYS_ANY_HIT;
-// Closest mode's result record: one 16-B store by the quad's first lane (16), or a dword per lane (4;
-// A/B builds, measured alike: DESIGN.md §14).
-#ifndef BM_RAYS_HIT_STORE
-#define BM_RAYS_HIT_STORE 16
-#endif
 
 __device__ __forceinline__ bool finite3(const vec3f a) {
     return fabsf(a.x) < __builtin_inff() && fabsf(a.y) < __builtin_inff() && fabsf(a.z) < __builtin_inff();
@@ -29,24 +24,12 @@ __device__ __forceinline__ bool finite3(const vec3f a) {
 // closest mode: tmax NaN or <= 0) is finished here without traversal, so no NaN reaches a traversal
 // loop: the miss record, or 0.
 template <int MODE, bool COUNT, uint32_t PRIO>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : BM_QUAD_WAVES))) void
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : QUAD_WAVES))) void
 k_query_rays(const TraceParams p) {
     __shared__ uint2 s_stk[QUAD_LDS][QRAYS];
-#if BM_QUAD_LEAF_LDS
-    __shared__ float4 s_lt[QRAYS][12];
-#endif
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int c = lane & 3, q = lane >> 2;
-    QStack<QUAD_LDS> st;
-    st.s = s_stk;
-#if BM_QUAD_LEAF_LDS
-    st.lt = s_lt[w * 16 + q];
-#endif
-    st.ray = w * 16 + q;
-    st.g_ref = p.ovf_ref;
-    st.g_t = p.ovf_t;
-    st.slot = blockIdx.x * QRAYS + st.ray;
-    st.stride = p.ovf_stride;
+    const QStack<QUAD_LDS> st = quad_stack<QUAD_LDS>(p, s_stk, w * 16 + q);
     unsigned long long cn = 0, ct = 0, ch = 0;
     const unsigned long long none[3] = {0, 0, 0};
     const uint32_t n = p.q_n;
@@ -70,11 +53,9 @@ k_query_rays(const TraceParams p) {
                 if (ibest == NO_TRI) tbest = __builtin_inff();
                 else if (COUNT && c == 0) ++ch;
             }
-#if BM_RAYS_HIT_STORE == 16
+            // the result record: one 16-B store by the quad's first lane (a dword per lane measured
+            // alike: DESIGN.md §14)
             if (c == 0) reinterpret_cast<float4*>(p.q_out)[sidx] = make_float4(tbest, bu, bv, u2f(ibest));
-#else
-            reinterpret_cast<float*>(p.q_out)[4 * (size_t)sidx + c] = c == 0 ? tbest : c == 1 ? bu : c == 2 ? bv : u2f(ibest);
-#endif
         } else {
             bool occ = false;
             if (valid && p.num_tris) {  // quad_anyhit starts at the root without looking at num_tris

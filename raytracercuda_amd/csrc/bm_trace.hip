@@ -1,7 +1,8 @@
 // bm_trace.hip — per-pixel primary-ray trace for gfx950 (replaces bmMarchKernel,
 // Raytracer/BuildTree.cu:367-499; Trace.cu and Trace2.cu carry no live semantics).
 //
-// The product kernels (device code in bm_trace_dev.h):
+// The product kernels (device code in bm_trace_quad.h, bm_trace_packet.h and bm_trace_lanes.h; what
+// they share in bm_trace_dev.h):
 //   k_trace_quad    ray quads (four lanes per ray over the BVH4, 4x4 pixels per wave), persistent
 //                   grid, block-dynamic LDS tile tickets, XCD-aware runs, cost-ordered schedule;
 //                   primary rays or primary + fused shadow rays
@@ -14,7 +15,9 @@
 // reference's exact arithmetic (Camera.cpp:51-66), so no 12-byte-per-pixel ray table is read.
 // Traversal stacks live in LDS, with a global overflow area indexed by the thread's slot in the
 // persistent grid (no scratch).
-#include "bm_trace_dev.h"
+#include "bm_trace_lanes.h"
+#include "bm_trace_packet.h"
+#include "bm_trace_quad.h"
 
 namespace bm {
 namespace {
@@ -101,16 +104,7 @@ __global__ __launch_bounds__(256) void k_reshade(const TraceParams p, const floa
         float t = 0.f, u = 0.f, v = 0.f;
         (void)tri_test(tri_orig[3 * (size_t)id], tri_orig[3 * (size_t)id + 1], tri_orig[3 * (size_t)id + 2], eye, dir,
                        t, u, v);
-        // bmFaceInterpolate<vec3> + normalize + pack (CudaComon.cuh:253-266, BuildTree.cu:489-491)
-        const float* n = p.nrm + 9 * (size_t)id;
-        const float ww = 1.f - (u + v);
-        const vec3f nn = v3((n[0] * ww + n[3] * u) + n[6] * v, (n[1] * ww + n[4] * u) + n[7] * v,
-                            (n[2] * ww + n[5] * u) + n[8] * v);
-        const float il = 1.f / sqrtf(dot(nn, nn));
-        const float z = nn.z * il;
-        const float rr = fabsf(z * 255.f);
-        packed = ((rr == rr) ? (uint32_t)rr : 0u) << 16;
-        nzv = fabsf(z);
+        packed = shade_hit(p, id, u, v, nzv);
         tout = t;
     }
     p.packed[(size_t)y * p.pitch_u32 + x] = packed;
@@ -147,15 +141,9 @@ hipError_t launch_variant(const TraceParams& p, int variant, hipStream_t s, uint
             // wave packets: BVH4 primary rays, non-counting (a packet's visit order is not the oracle's)
             if constexpr (W == 4 && SH == SH_NONE && !COUNT) {
                 const uint32_t tiles = ((p.width + 7) / 8) * ((p.local_rows + 7) / 8);
-                if (BM_PK_SCHED == 0) {
-                    if (grid) *grid = 0;
-                    if (p.diag) k_trace_packet<SH_NONE, true><<<(tiles + WAVES - 1) / WAVES, BLOCK, 0, s>>>(p);
-                    else k_trace_packet<SH_NONE><<<(tiles + WAVES - 1) / WAVES, BLOCK, 0, s>>>(p);
-                } else if (p.diag) {
-                    launch_persistent(k_trace_packet<SH_NONE, true>, p, s, grid);
-                } else {
-                    launch_persistent(k_trace_packet<SH_NONE>, p, s, grid);
-                }
+                if (grid) *grid = 0;
+                if (p.diag) k_trace_packet<SH_NONE, true><<<(tiles + WAVES - 1) / WAVES, BLOCK, 0, s>>>(p);
+                else k_trace_packet<SH_NONE><<<(tiles + WAVES - 1) / WAVES, BLOCK, 0, s>>>(p);
                 break;
             }
             [[fallthrough]];

@@ -7,10 +7,12 @@
 //   k_trace_pair         two lanes per ray (8x4 pixels per wave): +5-16 % against quads
 //   k_trace_quad_fetch   ray quads with in-wave ray refill: slower than block-dynamic tiles
 //   k_trace_quad<.., 8>  BVH8 records, two children per lane: 12-16 % slower than BVH4
+// They build on the single-lane and quad device code (bm_trace_lanes.h, bm_trace_quad.h).
 // Each gives the oracle's frames and counters exactly like the product kernels (same traversal
 // order), which the A/B build's variant tests check.
 #if BM_TRACE_AB
-#include "bm_trace_dev.h"
+#include "bm_trace_lanes.h"
+#include "bm_trace_quad.h"
 
 namespace bm {
 namespace {
@@ -146,19 +148,12 @@ __device__ __forceinline__ void pair_closest(const TraceParams& p, const PS& st,
 // Persistent pair kernel: 8x4 pixel tiles handed to the block's waves from an LDS ticket (the
 // block's share in screen order, XCD-aware runs as in k_trace_quad; frames do not depend on it).
 template <bool COUNT, int LDS_N, uint32_t PRIO>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : BM_QUAD_WAVES))) void k_trace_pair(const TraceParams p) {
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : QUAD_WAVES))) void k_trace_pair(const TraceParams p) {
     __shared__ uint2 s_stk[LDS_N][PRAYS];
     __shared__ uint32_t s_ticket;
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const uint32_t h = (uint32_t)lane & 1u, r = (uint32_t)lane >> 1;
-    QStack<LDS_N, PRAYS> st;
-    st.s = s_stk;
-    st.ray = w * 32 + (int)r;
-    const uint32_t slot = blockIdx.x * PRAYS + st.ray;
-    st.g_ref = p.ovf_ref;
-    st.g_t = p.ovf_t;
-    st.slot = slot;
-    st.stride = p.ovf_stride;
+    const QStack<LDS_N, PRAYS> st = quad_stack<LDS_N>(p, s_stk, w * 32 + (int)r);
     const uint32_t tiles_x = (p.width + 7) / 8, tiles_y = (p.local_rows + 3) / 4;
     const uint32_t ntiles = tiles_x * tiles_y;
     const vec3f eye = v3(p.eye[0], p.eye[1], p.eye[2]);
@@ -217,14 +212,7 @@ __global__ __launch_bounds__(BLOCK) BM_TRACE_OCCUPANCY void k_trace_quad_fetch(c
     __shared__ uint2 s_stk[LDS_N][QRAYS];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int c = lane & 3, q = lane >> 2;
-    QStack<LDS_N> st;
-    st.s = s_stk;
-    st.ray = w * 16 + q;
-    const uint32_t slot = blockIdx.x * QRAYS + st.ray;
-    st.g_ref = p.ovf_ref;
-    st.g_t = p.ovf_t;
-    st.slot = slot;
-    st.stride = p.ovf_stride;
+    const QStack<LDS_N> st = quad_stack<LDS_N>(p, s_stk, w * 16 + q);
     const uint32_t tiles_x = (p.width + 3) / 4, tiles_y = (p.local_rows + 3) / 4;
     const uint32_t ntiles = tiles_x * tiles_y;
     const uint32_t nwaves = gridDim.x * WAVES;
@@ -292,15 +280,7 @@ __global__ __launch_bounds__(BLOCK) BM_TRACE_OCCUPANCY void k_trace_quad_fetch(c
                 uint32_t packed = MISS_PACKED;
                 float nzv = 0.0f;
                 if (ibest != NO_TRI) {
-                    const float* n = p.nrm + 9 * (size_t)ibest;
-                    const float ww = 1.f - (bu + bv);
-                    const vec3f nn = v3((n[0] * ww + n[3] * bu) + n[6] * bv, (n[1] * ww + n[4] * bu) + n[7] * bv,
-                                        (n[2] * ww + n[5] * bu) + n[8] * bv);
-                    const float il = 1.f / sqrtf(dot(nn, nn));
-                    const float z = nn.z * il;
-                    const float rr = fabsf(z * 255.f);
-                    packed = ((rr == rr) ? (uint32_t)rr : 0u) << 16;
-                    nzv = fabsf(z);
+                    packed = shade_hit(p, ibest, bu, bv, nzv);
                     if (COUNT && c == 0) ++ch;
                 }
                 if (c == 0) p.packed[(size_t)lr * p.pitch_u32 + x] = packed;
