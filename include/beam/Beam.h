@@ -134,6 +134,14 @@ inline void setHashGridMode(bool on) {
     if (on) detail::flags_slot() = (detail::flags_slot() | BM_OPT_REFERENCE_HASH) & ~BM_OPT_REFERENCE_KD;
     else detail::flags_slot() &= ~BM_OPT_REFERENCE_HASH;
 }
+// A column-major 4x4 (16 floats, glm::mat4's memory layout: element (r, c) at m[4*c + r]) as the 12-float
+// row-major 3x4 transform of IScene::addInstance; the fourth row is dropped (an affine matrix has 0,0,0,1 there).
+inline void xformFromColumnMajor4x4(const float colMajor16[16], float xformOut[12]) {
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) xformOut[4 * r + c] = colMajor16[4 * c + r];
+}
+// The map an instance's normals go through: the cofactor matrix of xform's linear part, row-major 3x3.
+inline u32 normalMatrix(const float xform[12], float out9[9]) { return (u32)bm_xform_normal_matrix(xform, out9); }
 inline u32 sync() { return (u32)bm_sync(detail::ctx()); }
 inline std::string lastError() { return bm_last_error_string(detail::ctx()); }
 
@@ -252,6 +260,26 @@ class IScene {
     u32 hitAttributes(const bm_hit* deviceHits, u32 n, const bm_attr_req* reqs, u32 numReqs) {
         return (u32)bm_scene_hit_attributes(h_, deviceHits, n, reqs, numReqs);
     }
+    // Extension: instance transforms (include/beam_c.h, "instance transforms"). xform: 12 floats, row-major
+    // 3x4 (xformFromColumnMajor4x4 converts a glm::mat4's 16 floats). addInstance appends the mesh at that
+    // placement and reports the entry's index; setInstanceTransform takes effect at the next updateGPUScene
+    // or refitGPUScene; removeInstance erases the entry at index, plain or instance.
+    u32 addInstance(const sptr<IMesh>& mesh, const float xform[12], u32* index = nullptr) {
+        if (!mesh) return ERROR_INVALID_PARAMETER;
+        const u32 e = (u32)bm_scene_add_instance(h_, mesh->handle(), xform, index);
+        if (e == ERROR_ALL_FINE) meshes_.push_back(mesh);
+        return e;
+    }
+    u32 addInstance(IMesh* mesh, const float xform[12], u32* index = nullptr) {  // the caller keeps the mesh alive
+        return (u32)bm_scene_add_instance(h_, mesh ? mesh->handle() : nullptr, xform, index);
+    }
+    u32 setInstanceTransform(u32 index, const float xform[12]) {
+        return (u32)bm_scene_set_instance_transform(h_, index, xform);
+    }
+    u32 instanceTransform(u32 index, float xformOut[12]) const {
+        return (u32)bm_scene_get_instance_transform(h_, index, xformOut);
+    }
+    u32 removeInstance(u32 index) { return (u32)bm_scene_remove_instance(h_, index); }
     bm_scene* handle() const { return h_; }
 
    private:

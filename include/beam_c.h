@@ -378,6 +378,60 @@ typedef struct bm_attr_req {
 int32_t bm_scene_hit_attributes(bm_scene* s, const bm_hit* hits_dev, uint32_t n, const bm_attr_req* reqs,
                                 uint32_t num_reqs);
 
+/* ---- instance transforms: place a mesh many times, move it by refit -----------------------------
+ * The reference has no transforms: its Model::load can add one mesh numAdds times, every copy on the same
+ * spot. bm_scene_add_instance adds "this mesh, at this 3x4 matrix" as one more entry of the scene's list.
+ * A transform is 12 floats, row-major 3x4: element (r, c) is xform[4*r + c], the linear part
+ * L[r][c] = xform[4*r + c] (c < 3), the translation xform[4*r + 3] — the layout of VkTransformMatrixKHR,
+ * OptiX and Embree.
+ * Flattened instancing: every instance entry gets its own triangle records, as every added mesh does. The
+ * scene owns world-space copies of an instance's positions and normals, written by one kernel launch on the
+ * context stream at the start of every bm_scene_build and bm_scene_refit (inside build_ms); the build reads
+ * those instead of the mesh's own slots. A scene without instance entries enqueues exactly what it did before.
+ * Entries and indices: an entry's position in the list (plain entries of bm_scene_add_mesh and instance
+ *   entries counted alike, in the order added) is its index: the m that BM_ATTR_MESH_FACE reports, and the
+ *   order in which global triangle ids are assigned. Removing an earlier entry shifts later ones down by one.
+ *   A mesh may be added any number of times, as a plain entry and as an instance alike.
+ * Arithmetic, float32, one rounding per operation in the order written, never contracted into fused
+ *   multiply-adds (results are reproducible bit for bit by the same statements in any IEEE float32):
+ *     position  p'[r] = ((x[4r]*p.x + x[4r+1]*p.y) + x[4r+2]*p.z) + x[4r+3]            r = 0, 1, 2
+ *     normal    n'[r] = (C[r][0]*n.x + C[r][1]*n.y) + C[r][2]*n.z
+ *   C is the cofactor matrix of L (its inverse transpose times its determinant), computed on the host by
+ *   bm_xform_normal_matrix, which the build itself calls:
+ *     c00 = L11*L22 - L12*L21   c01 = L12*L20 - L10*L22   c02 = L10*L21 - L11*L20
+ *     c10 = L02*L21 - L01*L22   c11 = L00*L22 - L02*L20   c12 = L01*L20 - L00*L21
+ *     c20 = L01*L12 - L02*L11   c21 = L02*L10 - L00*L12   c22 = L00*L11 - L01*L10
+ *   Normals are not renormalised and their sign is not fixed up for mirroring matrices (det L < 0 flips
+ *   them): the trace normalises after interpolation, and interpolation commutes with a linear map. A singular
+ *   matrix is accepted; it makes degenerate triangles, as a caller's own vertices can.
+ * Hit attributes (bm_scene_hit_attributes): BM_VERTEX_DATA_POSITION, BM_VERTEX_DATA_NORMAL and
+ *   BM_ATTR_GEOM_NORMAL of a hit on an instance entry are in world space, as of the last build or refit
+ *   (a bm_mesh_set_vertex_data of positions or normals after it is not seen before the next one). Every other
+ *   slot — UVs, TANGENT, BITANGENT, the EXTRAs — is the mesh's own, as uploaded: BM_ATTR_MESH_FACE's m with
+ *   bm_scene_get_instance_transform and bm_xform_normal_matrix give a caller what it needs to transform
+ *   tangents itself. An instance whose mesh now indexes vertices past the vertex count of that build or refit
+ *   gives BM_ERROR_NOT_BUILT.
+ * On a multi-device context every replica transforms its own copy. Works with BVH4, BVH2 and both reference
+ * modes; bm_scene_refit's "same meshes, same triangle counts" rule is unchanged.
+ * Errors of the calls below: BM_ERROR_INVALID_PARAMETER for a null handle or matrix, a non-finite matrix
+ * element, an index past the list, a mesh of another context. */
+/* Appends an instance entry and marks the scene unbuilt, as bm_scene_add_mesh does; *index_out (may be NULL)
+ * receives the entry's index. */
+int32_t bm_scene_add_instance(bm_scene* s, bm_mesh* m, const float xform[12], uint32_t* index_out);
+/* Replaces the entry's matrix; launches nothing and does not mark the scene unbuilt. The new placement takes
+ * effect at the next bm_scene_build or bm_scene_refit; until then traces, ray queries and hit attributes all
+ * see the old one. index must name an entry made by bm_scene_add_instance. Rigid animation is this call per
+ * moved object plus one bm_scene_refit. */
+int32_t bm_scene_set_instance_transform(bm_scene* s, uint32_t index, const float xform[12]);
+/* The matrix last set for an instance entry (not necessarily the one of the last build); a plain entry is
+ * BM_ERROR_INVALID_PARAMETER. */
+int32_t bm_scene_get_instance_transform(const bm_scene* s, uint32_t index, float xform_out[12]);
+/* Erases the entry at index, plain or instance, and marks the scene unbuilt. bm_scene_remove_mesh keeps its
+ * behaviour: it erases the first entry whose mesh is m, of either kind. */
+int32_t bm_scene_remove_instance(bm_scene* s, uint32_t index);
+/* The cofactor matrix C above, row-major 3x3, of xform's linear part. Host only: no context, no device. */
+int32_t bm_xform_normal_matrix(const float xform[12], float out9[9]);
+
 /* ---- camera: ICamera (Beam.h:65-72, Camera.cpp) ----------------------------------------- */
 int32_t bm_camera_create(bm_context* ctx, bm_camera** out);
 /* setInitialRays (Camera.cpp:43-72): same sequential ray recurrence and validation. */
@@ -515,6 +569,9 @@ int32_t bm_model_mesh(const bm_model* m, uint32_t i, const float** pos, const fl
  * scene is non-NULL, add each to it num_adds times. The meshes belong to the model: remove them
  * from scenes (or destroy the scenes) before bm_model_destroy. */
 int32_t bm_model_upload(bm_model* m, bm_context* ctx, bm_scene* scene, uint32_t num_adds);
+/* The same upload (once per model), then every mesh added to scene as an instance entry with the one
+ * matrix (bm_scene_add_instance), in mesh order. */
+int32_t bm_model_add_instance(bm_model* m, bm_context* ctx, bm_scene* scene, const float xform[12]);
 /* Tangents and bitangents of mesh i (3 floats per vertex), NULL when the mesh has no normals or no UVs. */
 int32_t bm_model_mesh_tangents(const bm_model* m, uint32_t i, const float** tangent, const float** bitangent);
 bm_mesh* bm_model_gpu_mesh(const bm_model* m, uint32_t i);

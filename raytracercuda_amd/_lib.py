@@ -143,6 +143,12 @@ SIGNATURES = {
     "bm_scene_create": (_I, [_P, C.POINTER(_P)]),
     "bm_scene_add_mesh": (_I, [_P, _P]),
     "bm_scene_remove_mesh": (_I, [_P, _P]),
+    "bm_scene_add_instance": (_I, [_P, _P, _FP, _UP]),
+    "bm_scene_set_instance_transform": (_I, [_P, _U, _FP]),
+    "bm_scene_get_instance_transform": (_I, [_P, _U, _FP]),
+    "bm_scene_remove_instance": (_I, [_P, _U]),
+    "bm_xform_normal_matrix": (_I, [_FP, _FP]),
+    "bm_model_add_instance": (_I, [_P, _P, _P, _FP]),
     "bm_scene_build": (_I, [_P, C.POINTER(BuildStats)]),
     "bm_scene_refit": (_I, [_P, C.POINTER(BuildStats)]),
     "bm_scene_kd_stats": (_I, [_P, _U64P]),

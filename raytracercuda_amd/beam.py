@@ -44,6 +44,30 @@ def _up(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
+def _xform12(xform) -> np.ndarray:
+    """An instance transform as 12 contiguous float32, row-major 3x4: from 12 floats, a (3,4) array, or a
+    (4,4) array whose last row is exactly [0,0,0,1]. Anything else is a ValueError."""
+    a = np.asarray(xform, dtype=np.float32)
+    if a.shape == (4, 4):
+        if not np.array_equal(a[3], np.array([0, 0, 0, 1], np.float32)):
+            raise ValueError("xform: the last row of a (4,4) transform must be exactly [0,0,0,1]")
+        a = a[:3]
+    elif a.shape not in ((12,), (3, 4)):
+        raise ValueError(f"xform: expected 12 floats, a (3,4) or a (4,4) array, got shape {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(12)
+
+
+def normal_matrix(xform) -> np.ndarray:
+    """bm_xform_normal_matrix: the (3,3) cofactor matrix of the transform's linear part, the map an instance's
+    normals go through (host only; include/beam_c.h has the formula)."""
+    x = _xform12(xform)
+    out = np.zeros(9, np.float32)
+    err = _lib.load().bm_xform_normal_matrix(_fp(x), _fp(out))
+    if err:
+        raise BeamError(err, "bm_xform_normal_matrix")
+    return out.reshape(3, 3)
+
+
 def comm_unique_id() -> bytes:
     """Rank 0 of a multi-process context makes the RCCL unique id every rank passes as comm_id."""
     lib = _lib.load()
@@ -240,6 +264,30 @@ class IScene:
     def removeMesh(self, mesh: IMesh):
         self.ctx._check(self.ctx.lib.bm_scene_remove_mesh(self.h, mesh.h))
         self.meshes = [m for m in self.meshes if m is not mesh]
+
+    def addInstance(self, mesh: IMesh, xform) -> int:
+        """bm_scene_add_instance: the mesh placed by a 3x4 transform (12 floats, (3,4), or (4,4) with last row
+        [0,0,0,1]) as one more entry of the scene; returns the entry's index (what ATTR_MESH_FACE reports)."""
+        x = _xform12(xform)
+        idx = C.c_uint32(0)
+        self.ctx._check(self.ctx.lib.bm_scene_add_instance(self.h, mesh.h, _fp(x), C.byref(idx)))
+        self.meshes.append(mesh)
+        return int(idx.value)
+
+    def setInstanceTransform(self, index: int, xform) -> None:
+        """Replace an instance entry's matrix; it takes effect at the next updateGPUScene or refitGPUScene."""
+        x = _xform12(xform)
+        self.ctx._check(self.ctx.lib.bm_scene_set_instance_transform(self.h, index, _fp(x)))
+
+    def instanceTransform(self, index: int) -> np.ndarray:
+        """The matrix last set for an instance entry, (3,4) float32."""
+        out = np.zeros(12, np.float32)
+        self.ctx._check(self.ctx.lib.bm_scene_get_instance_transform(self.h, index, _fp(out)))
+        return out.reshape(3, 4)
+
+    def removeInstance(self, index: int) -> None:
+        """Erase the entry at index (plain or instance); later entries move down by one."""
+        self.ctx._check(self.ctx.lib.bm_scene_remove_instance(self.h, index))
 
     def updateGPUScene(self, stats: bool = False):
         """Rebuild the BVH from the current meshes (asynchronous unless stats=True)."""
@@ -697,6 +745,13 @@ class Model:
     def upload(self, ctx: "Context", scene: "IScene" = None, num_adds: int = 1):
         self.ctx = ctx
         ctx._check(self.lib.bm_model_upload(self.h, ctx.h, scene.h if scene is not None else None, num_adds))
+
+    def addInstance(self, ctx: "Context", scene: "IScene", xform) -> None:
+        """bm_model_add_instance: upload the model's meshes (once) and add each to scene as an instance entry
+        with the one transform."""
+        x = _xform12(xform)
+        self.ctx = ctx
+        ctx._check(self.lib.bm_model_add_instance(self.h, ctx.h, scene.h, _fp(x)))
 
     def gpu_mesh(self, i: int):
         return self.lib.bm_model_gpu_mesh(self.h, i)

@@ -136,6 +136,19 @@ struct bm_scene {
     bm_context* ctx = nullptr;
     std::vector<bm_scene*> rep;  // replicas on the context's peer devices
     std::vector<bm_mesh*> meshes;
+    // instance transforms (bm_xform.hip): entries[i] goes with meshes[i]. An instance entry's build reads the
+    // scene-owned world-space copies of its mesh's positions and normals, rewritten before every build and refit
+    struct Entry {
+        bool inst = false;      // made by bm_scene_add_instance
+        float x[12] = {};       // its transform, row-major 3x4
+        uint32_t built_nv = 0;  // the last build or refit filled the pools for this many vertices at pool_off
+        size_t pool_off = 0;    // floats from the start of inst_pos / inst_nrm (a multiple of 4)
+    };
+    std::vector<Entry> entries;
+    DevBuf inst_pos, inst_nrm, inst_table;  // the pools; the XformRow image of the last build
+    unsigned char* inst_staging = nullptr;  // pinned host copy of that image
+    size_t inst_staging_cap = 0;
+    hipEvent_t inst_done = nullptr;    // the last upload has left inst_staging
     bool built = false;
     uint32_t n = 0, nrec = 0, leaf_size = 4, width = 4;
     std::vector<std::pair<bm_mesh*, uint32_t>> built_with;  // meshes + triangle counts of the last build
@@ -728,17 +741,93 @@ int32_t bm_scene_add_mesh(bm_scene* s, bm_mesh* m) {
         if (rc) return peer_fail(s->ctx, s->rep[i]->ctx, rc);
     }
     s->meshes.push_back(m);
+    s->entries.emplace_back();
     s->built = false;
     return BM_ERROR_ALL_FINE;
+}
+
+// Erase entry i of the scene (and of its replicas, whose lists mirror the root's).
+static void scene_erase_entry(bm_scene* s, size_t i) {
+    for (bm_scene* r : s->rep) scene_erase_entry(r, i);
+    if (i >= s->meshes.size()) return;  // a replica whose add failed half way
+    s->meshes.erase(s->meshes.begin() + (ptrdiff_t)i);
+    s->entries.erase(s->entries.begin() + (ptrdiff_t)i);
+    s->built = false;
 }
 
 int32_t bm_scene_remove_mesh(bm_scene* s, bm_mesh* m) {
     if (!s || !m) return BM_ERROR_INVALID_PARAMETER;
     auto it = std::find(s->meshes.begin(), s->meshes.end(), m);
     if (it == s->meshes.end()) return fail(s->ctx, BM_ERROR_INVALID_PARAMETER, "removeMesh: mesh not in scene");
-    for (size_t i = 0; i < s->rep.size(); ++i) (void)bm_scene_remove_mesh(s->rep[i], m->rep[i]);
-    s->meshes.erase(it);  // the reference forgets to mark its mesh table dirty (Scene.cpp:43-56)
+    // the reference forgets to mark its mesh table dirty (Scene.cpp:43-56)
+    scene_erase_entry(s, (size_t)(it - s->meshes.begin()));
+    return BM_ERROR_ALL_FINE;
+}
+
+// ---- instance transforms (bm_xform.hip) ----------------------------------------------------------
+static bool xform_finite(const float* x) {
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(x[i])) return false;
+    return true;
+}
+
+int32_t bm_xform_normal_matrix(const float xform[12], float out9[9]) {
+    if (!xform || !out9) return BM_ERROR_INVALID_PARAMETER;
+    const float L00 = xform[0], L01 = xform[1], L02 = xform[2];
+    const float L10 = xform[4], L11 = xform[5], L12 = xform[6];
+    const float L20 = xform[8], L21 = xform[9], L22 = xform[10];
+    // float32, one rounding per operation (this file is built without contraction)
+    out9[0] = L11 * L22 - L12 * L21;
+    out9[1] = L12 * L20 - L10 * L22;
+    out9[2] = L10 * L21 - L11 * L20;
+    out9[3] = L02 * L21 - L01 * L22;
+    out9[4] = L00 * L22 - L02 * L20;
+    out9[5] = L01 * L20 - L00 * L21;
+    out9[6] = L01 * L12 - L02 * L11;
+    out9[7] = L02 * L10 - L00 * L12;
+    out9[8] = L00 * L11 - L01 * L10;
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_add_instance(bm_scene* s, bm_mesh* m, const float xform[12], uint32_t* index_out) {
+    if (!s || !m || !xform || m->ctx != s->ctx || m->rep.size() != s->rep.size()) return BM_ERROR_INVALID_PARAMETER;
+    if (!xform_finite(xform)) return fail(s->ctx, BM_ERROR_INVALID_PARAMETER, "addInstance: non-finite matrix element");
+    for (size_t i = 0; i < s->rep.size(); ++i) {
+        const int32_t rc = bm_scene_add_instance(s->rep[i], m->rep[i], xform, nullptr);
+        if (rc) return peer_fail(s->ctx, s->rep[i]->ctx, rc);
+    }
+    bm_scene::Entry e;
+    e.inst = true;
+    std::memcpy(e.x, xform, sizeof(e.x));
+    if (index_out) *index_out = (uint32_t)s->meshes.size();
+    s->meshes.push_back(m);
+    s->entries.push_back(e);
     s->built = false;
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_set_instance_transform(bm_scene* s, uint32_t index, const float xform[12]) {
+    if (!s || !xform) return BM_ERROR_INVALID_PARAMETER;
+    if (index >= s->entries.size() || !s->entries[index].inst)
+        return fail(s->ctx, BM_ERROR_INVALID_PARAMETER, "setInstanceTransform: not an instance entry of the scene");
+    if (!xform_finite(xform))
+        return fail(s->ctx, BM_ERROR_INVALID_PARAMETER, "setInstanceTransform: non-finite matrix element");
+    for (bm_scene* r : s->rep) (void)bm_scene_set_instance_transform(r, index, xform);
+    std::memcpy(s->entries[index].x, xform, sizeof(s->entries[index].x));  // read by the next build or refit
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_get_instance_transform(const bm_scene* s, uint32_t index, float xform_out[12]) {
+    if (!s || !xform_out) return BM_ERROR_INVALID_PARAMETER;
+    if (index >= s->entries.size() || !s->entries[index].inst) return BM_ERROR_INVALID_PARAMETER;
+    std::memcpy(xform_out, s->entries[index].x, sizeof(s->entries[index].x));
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_remove_instance(bm_scene* s, uint32_t index) {
+    if (!s) return BM_ERROR_INVALID_PARAMETER;
+    if (index >= s->entries.size()) return fail(s->ctx, BM_ERROR_INVALID_PARAMETER, "removeInstance: no such entry");
+    scene_erase_entry(s, index);
     return BM_ERROR_ALL_FINE;
 }
 
@@ -1052,7 +1141,14 @@ static int32_t scene_build_impl(bm_scene* s, bm_build_stats* stats, bool refit) 
     BM_HIP(ctx, ctx_drain(ctx));  // traces on render-target streams may still read the old build
     uint64_t n64 = 0;
     std::vector<bm::MeshDesc> table;
-    for (bm_mesh* m : s->meshes) {
+    // instance entries: one row each for k_instance_xform (pointers filled in once the pools are reserved); a
+    // region of 3 * nv floats per pool, rounded up to 16 bytes so that every region starts on such a boundary
+    std::vector<bm::XformRow> xrows;
+    std::vector<size_t> xentry, xoff;  // the rows' scene entries and their regions' first floats
+    size_t pool_floats = 0;
+    uint64_t units64 = 0;
+    for (size_t i = 0; i < s->meshes.size(); ++i) {
+        bm_mesh* m = s->meshes[i];
         if (!m->slot[BM_VERTEX_DATA_POSITION].p || m->slot_comp[BM_VERTEX_DATA_POSITION] != 3)
             return fail(ctx, BM_ERROR_NO_VERTICES, "mesh without a 3-component position slot");
         if (m->num_indices && !m->idx.p) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "mesh indices missing");
@@ -1069,8 +1165,23 @@ static int32_t scene_build_impl(bm_scene* s, bm_build_stats* stats, bool refit) 
         d.num_tris = m->num_indices / 3;
         n64 += d.num_tris;
         table.push_back(d);
+        if (s->entries[i].inst) {
+            bm::XformRow r{};
+            r.src_pos = d.pos;
+            r.src_nrm = d.nrm;
+            r.nv = m->num_vertices;
+            r.unit_first = (uint32_t)units64;
+            std::memcpy(r.x, s->entries[i].x, sizeof(r.x));
+            (void)bm_xform_normal_matrix(r.x, r.c);
+            xrows.push_back(r);
+            xentry.push_back(i);
+            xoff.push_back(pool_floats);
+            units64 += (m->num_vertices + (uint64_t)bm::XFORM_UNIT - 1) / bm::XFORM_UNIT;
+            pool_floats += (3 * (size_t)m->num_vertices + 3) & ~(size_t)3;
+        }
     }
     if (n64 >= bm::MAX_TRIS) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "more than 2^27 triangles");
+    if (units64 > 0xFFFFFFFFull) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "instances: more than 2^40 vertices");
     const uint32_t n = (uint32_t)n64;
     const uint32_t nrec = bm::num_records(n);
     const size_t ni = n > 1 ? n - 1 : 1;
@@ -1111,6 +1222,33 @@ static int32_t scene_build_impl(bm_scene* s, bm_build_stats* stats, bool refit) 
     BM_HIP(ctx, grow.reserve(s->records, (width == 8 ? 256 : width == 4 ? 128 : 64) * (size_t)nrec));
     if (width == 8) BM_HIP(ctx, grow.reserve(s->records2, 64 * (size_t)nrec));
     BM_HIP(ctx, grow.reserve(s->tris, 48 * nn));
+    const size_t ximage = (sizeof(bm::XformRow) + sizeof(uint32_t)) * xrows.size();
+    if (!xrows.empty()) {
+        BM_HIP(ctx, grow.reserve(s->inst_pos, sizeof(float) * pool_floats));
+        BM_HIP(ctx, grow.reserve(s->inst_nrm, sizeof(float) * pool_floats));
+        BM_HIP(ctx, grow.reserve(s->inst_table, ximage));
+        // the previous row upload must be done before its pinned staging buffer is rewritten
+        if (!s->inst_done) BM_HIP(ctx, hipEventCreateWithFlags(&s->inst_done, hipEventDisableTiming));
+        else BM_HIP(ctx, hipEventSynchronize(s->inst_done));
+        if (ximage > s->inst_staging_cap) {
+            if (s->inst_staging) (void)hipHostFree(s->inst_staging);
+            s->inst_staging = nullptr;
+            s->inst_staging_cap = 0;
+            BM_HIP(ctx, hipHostMalloc((void**)&s->inst_staging, ximage, hipHostMallocDefault));
+            s->inst_staging_cap = ximage;
+        }
+        uint32_t* prefix = reinterpret_cast<uint32_t*>(s->inst_staging + sizeof(bm::XformRow) * xrows.size());
+        for (size_t k = 0; k < xrows.size(); ++k) {
+            xrows[k].dst_pos = s->inst_pos.as<float>() + xoff[k];
+            xrows[k].dst_nrm = s->inst_nrm.as<float>() + xoff[k];
+            table[xentry[k]].pos = xrows[k].dst_pos;
+            table[xentry[k]].nrm = xrows[k].dst_nrm;
+            prefix[k] = xrows[k].unit_first;
+        }
+        std::memcpy(s->inst_staging, xrows.data(), sizeof(bm::XformRow) * xrows.size());
+        BM_HIP(ctx, hipMemcpyAsync(s->inst_table.p, s->inst_staging, ximage, hipMemcpyHostToDevice, ctx->stream));
+        BM_HIP(ctx, hipEventRecord(s->inst_done, ctx->stream));
+    }
     if (!table.empty()) {
         std::memcpy(s->staging, table.data(), sizeof(bm::MeshDesc) * table.size());
         BM_HIP(ctx, hipMemcpyAsync(s->mesh_table.p, s->staging, sizeof(bm::MeshDesc) * table.size(),
@@ -1154,6 +1292,16 @@ static int32_t scene_build_impl(bm_scene* s, bm_build_stats* stats, bool refit) 
     b.orig_written = &orig;
     s->replicas_clean = false;  // until this build's kernels are enqueued (a failed launch leaves them unknown)
     BM_HIP(ctx, hipEventRecord(s->ev0, ctx->stream));
+    if (!xrows.empty()) {  // the instances' world-space vertices, before anything reads the mesh table
+        const unsigned char* img = s->inst_table.as<const unsigned char>();
+        BM_HIP(ctx, bm::launch_instance_xform(reinterpret_cast<const bm::XformRow*>(img),
+                                              reinterpret_cast<const uint32_t*>(img + sizeof(bm::XformRow) * xrows.size()),
+                                              (uint32_t)xrows.size(), (uint32_t)units64, ctx->stream));
+        for (size_t k = 0; k < xrows.size(); ++k) {
+            s->entries[xentry[k]].built_nv = xrows[k].nv;
+            s->entries[xentry[k]].pool_off = xoff[k];
+        }
+    }
     if (ctx->reference_kd || ctx->reference_hash) {
         if (refit) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "refit: not available in reference mode");
         const int32_t e = ctx->reference_kd ? kd_build(ctx, s, b, grow) : hash_build(ctx, s, b, grow);
@@ -1355,8 +1503,11 @@ void bm_scene_destroy(bm_scene* s) {
                       &s->kd_leaf_of, &s->kd_leaf_key, &s->kd_leaf_start, &s->kd_leaf_count,
                       &s->kd_lch, &s->kd_rch, &s->kd_first, &s->kd_last, &s->kd_pleaf, &s->kd_pint, &s->kd_nodes, &s->kd_cnodes,
                       &s->kd_leafrec, &s->kd_ftris, &s->kd_node_key, &s->kd_ubox, &s->kd_cache,
-                      &s->kd_queue, &s->kd_fill, &s->hash_bstart, &s->hash_bend, &s->attr_table})
+                      &s->kd_queue, &s->kd_fill, &s->hash_bstart, &s->hash_bend, &s->attr_table, &s->inst_pos,
+                      &s->inst_nrm, &s->inst_table})
         b->release();
+    if (s->inst_staging) (void)hipHostFree(s->inst_staging);
+    if (s->inst_done) (void)hipEventDestroy(s->inst_done);
     if (s->attr_staging) (void)hipHostFree(s->attr_staging);
     if (s->attr_done) (void)hipEventDestroy(s->attr_done);
     if (s->staging) (void)hipHostFree(s->staging);
@@ -1848,6 +1999,15 @@ int32_t bm_scene_hit_attributes(bm_scene* s, const bm_hit* hits_dev, uint32_t n,
             const bool has = m->slot[k].p && m->slot_comp[k];
             d.slot[k] = has ? m->slot[k].as<const float>() : nullptr;
             have[k] += has;
+        }
+        const bm_scene::Entry& en = s->entries[i];
+        if (en.inst) {
+            // world-space positions and normals, as of the last build or refit: the pools hold built_nv vertices
+            if (m->num_indices && m->max_index >= en.built_nv)
+                return fail(ctx, BM_ERROR_NOT_BUILT,
+                            "hit_attributes: an instance's mesh indexes vertices past those of the last build or refit");
+            d.slot[BM_VERTEX_DATA_POSITION] = s->inst_pos.as<const float>() + en.pool_off;
+            d.slot[BM_VERTEX_DATA_NORMAL] = s->inst_nrm.as<const float>() + en.pool_off;
         }
         for (uint32_t r = 0; r < num_reqs; ++r)
             if (p.req[r].kind == bm::ATTR_SLOT && d.slot[p.req[r].slot] && m->slot_comp[p.req[r].slot] != p.req[r].comps)

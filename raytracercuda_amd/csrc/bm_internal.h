@@ -246,6 +246,26 @@ struct AttrParams {
 };
 hipError_t launch_hit_attrs(const AttrParams& p, hipStream_t s);
 
+// ---- instance transforms (bm_xform.hip): world-space copies of instanced meshes' positions and normals ----
+// One row per instance entry of the scene, in scene order; uploaded as a byte image, followed by the rows'
+// unit_first again, packed for the search.
+constexpr uint32_t XFORM_UNIT = 256;  // vertices per work unit (one wave, four per lane)
+struct XformRow {
+    const float* src_pos;  // the mesh's own slots, 3 floats per vertex
+    const float* src_nrm;
+    float* dst_pos;        // the entry's 16-byte aligned regions of the scene's pools
+    float* dst_nrm;
+    uint32_t nv;           // vertices
+    uint32_t unit_first;   // work units of the entries before this one
+    float x[12];           // the transform, row-major 3x4
+    float c[9];            // bm_xform_normal_matrix(x)
+    uint32_t pad;
+};  // 128 B
+static_assert(sizeof(XformRow) == 128, "XformRow is uploaded as a byte image: no padding");
+// One launch for all rows: num_units = the sum of ceil(nv / XFORM_UNIT); prefix[e] = rows[e].unit_first.
+hipError_t launch_instance_xform(const XformRow* rows, const uint32_t* prefix, uint32_t num_entries,
+                                 uint32_t num_units, hipStream_t s);
+
 // ---- reference mode (bm_kd.hip): the reference's kd-tree and march ---------------------------------
 struct KdBuild {
     const MeshDesc* meshes;

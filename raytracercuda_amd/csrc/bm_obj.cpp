@@ -428,6 +428,16 @@ int32_t bm_model_upload(bm_model* m, bm_context* ctx, bm_scene* scene, uint32_t 
     return BM_ERROR_ALL_FINE;
 }
 
+// The same upload (once), then every mesh added to scene as an instance with one matrix.
+int32_t bm_model_add_instance(bm_model* m, bm_context* ctx, bm_scene* scene, const float xform[12]) {
+    if (!m || !ctx || !scene || !xform) return BM_ERROR_INVALID_PARAMETER;
+    int32_t e = bm_model_upload(m, ctx, nullptr, 0);
+    if (e) return e;
+    for (bm_mesh* g : m->gpu)
+        if ((e = bm_scene_add_instance(scene, g, xform, nullptr))) return e;
+    return BM_ERROR_ALL_FINE;
+}
+
 int32_t bm_model_mesh_tangents(const bm_model* m, uint32_t i, const float** tangent, const float** bitangent) {
     if (!m || i >= m->meshes.size()) return BM_ERROR_INVALID_PARAMETER;
     const ObjMesh& mesh = m->meshes[i];
