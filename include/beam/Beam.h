@@ -260,6 +260,12 @@ class IScene {
     u32 hitAttributes(const bm_hit* deviceHits, u32 n, const bm_attr_req* reqs, u32 numReqs) {
         return (u32)bm_scene_hit_attributes(h_, deviceHits, n, reqs, numReqs);
     }
+    // Extension: the nearest triangle to each of n points in device memory (bm_scene_closest_points;
+    // asynchronous on the context stream): distance, barycentrics and triangle id as bm_hit records, which
+    // hitAttributes turns into the closest point (BM_VERTEX_DATA_POSITION), its normal or its mesh and face.
+    u32 closestPoints(const bm_point* devicePoints, u32 n, bm_hit* deviceHits) {
+        return (u32)bm_scene_closest_points(h_, devicePoints, n, 0, deviceHits);
+    }
     // Extension: instance transforms (include/beam_c.h, "instance transforms"). xform: 12 floats, row-major
     // 3x4 (xformFromColumnMajor4x4 converts a glm::mat4's 16 floats). addInstance appends the mesh at that
     // placement and reports the entry's index; setInstanceTransform takes effect at the next updateGPUScene

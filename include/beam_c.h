@@ -328,6 +328,64 @@ int32_t bm_scene_trace_rays(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uin
 int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode,
                                      uint32_t flags, void* out_dev, uint64_t out[3]);
 
+/* ---- closest-point queries: the nearest triangle to each point of a batch ----------------------
+ * For point i: which triangle of the scene is nearest, how far, and where on it — unsigned distance
+ * fields, point-cloud-to-mesh losses, proximity tests, snapping and projecting points onto a surface.
+ * A distance-ordered traversal of the same BVH4, pruned by box distance.
+ * points_dev and out_dev are device pointers on the context's device, 16-byte aligned. The work is
+ * enqueued on the context stream and the call returns without waiting; bm_sync waits. On a
+ * multi-device context the query runs on the root device alone.
+ * Result i is a bm_hit: t the distance sqrtf(dd), u and v the barycentrics of the closest point in
+ *   the hit-attribute convention (the point is v0*(1-(u+v)) + v1*u + v2*v), tri_id the global id. It
+ *   feeds bm_scene_hit_attributes as it is: BM_VERTEX_DATA_POSITION is then the closest point,
+ *   BM_VERTEX_DATA_NORMAL the normal there, BM_ATTR_MESH_FACE the owner (instanced scenes included:
+ *   their triangles are in world space).
+ * The winner is the lexicographic minimum of (dd_g, g) over ALL triangles g of the scene with
+ *   dd_g <= rmax*rmax (one float32 multiply; rmax = +inf: unbounded): equal dd resolves to the lowest
+ *   id. Without such a triangle, over an empty scene and for an invalid point (a non-finite component
+ *   of p; rmax NaN or <= 0) the record is the ray query's miss: t = +inf, u = v = 0, tri_id =
+ *   BM_NO_TRIANGLE.
+ * dd_g is this function of p and the triangle's v0, e1 = v1 - v0, e2 = v2 - v0 (each one float32
+ *   subtraction per component), in float32, one rounding per operation in the order written, never
+ *   contracted; dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z; a comparison with NaN is false:
+ *     ap = p - v0
+ *     d1 = dot(e1,ap)   d2 = dot(e2,ap)
+ *     a11 = dot(e1,e1)  a12 = dot(e1,e2)  a22 = dot(e2,e2)
+ *     d3 = d1 - a11     d4 = d2 - a12     d5 = d1 - a12     d6 = d2 - a22
+ *     1. d1 <= 0 && d2 <= 0                          -> u = 0, v = 0
+ *     2. d3 >= 0 && d4 <= d3                         -> u = 1, v = 0
+ *     3. vc = d1*d4 - d3*d2;  vc <= 0 && d1 >= 0 && d3 <= 0
+ *                                                    -> u = d1 / (d1 - d3), v = 0
+ *     4. d6 >= 0 && d5 <= d6                         -> u = 0, v = 1
+ *     5. vb = d5*d2 - d1*d6;  vb <= 0 && d2 >= 0 && d6 <= 0
+ *                                                    -> u = 0, v = d2 / (d2 - d6)
+ *     6. va = d3*d6 - d5*d4;  s = d4 - d3; r = d5 - d6;  va <= 0 && s >= 0 && r >= 0
+ *                                                    -> w = s / (s + r);  u = 1 - w, v = w
+ *     7. otherwise   den = 1 / ((va + vb) + vc);        u = vb*den, v = vc*den
+ *     q = ap - (e1*u + e2*v)   per component: ap.x - (e1.x*u + e2.x*v)
+ *     dd = dot(q,q)
+ *   The first matching region wins; divisions and sqrtf are correctly rounded. A triangle whose dd is
+ *   NaN is never a candidate (dd < best is false). A zero-area triangle has va = vb = vc = 0 up to
+ *   rounding: it counts through its vertex regions and through an edge region whose division is not
+ *   0/0, and where rounding sends it to region 7 with a zero sum it does not count at all — as rays do
+ *   not hit degenerate triangles either.
+ * flags: none defined yet, pass 0. Points are taken in the order given, 16 consecutive points per wave.
+ * BM_ERROR_INVALID_PARAMETER: a null handle, a null pointer with n > 0, a misaligned pointer, a flag
+ * bit, a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT: the scene has no current
+ * build. n = 0 succeeds without a launch. */
+typedef struct bm_point {
+    float p[3];
+    float rmax;
+} bm_point; /* 16 B */
+int32_t bm_scene_closest_points(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t flags,
+                                bm_hit* out_dev);
+/* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle evaluations,
+ * out[2] points with a result, out[3] the largest number of stack entries any query held at once (above
+ * 24 the traversal used the global overflow area); invalid points count nothing. Results are written
+ * exactly as bm_scene_closest_points writes them. Synchronous. */
+int32_t bm_scene_closest_points_counters(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t flags,
+                                         bm_hit* out_dev, uint64_t out[4]);
+
 /* ---- hit attributes: the meshes' vertex slots interpolated at ray-query hits ------------------
  * The reference's bmFaceInterpolate<T>(face, u, v, meshData, dataIdx) (CudaComon.cuh:253-266) over n
  * bm_hit records in device memory (as bm_scene_trace_rays writes them, or made by the caller): what a

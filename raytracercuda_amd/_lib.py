@@ -93,6 +93,11 @@ class Hit(C.Structure):
 RAYS_CLOSEST, RAYS_ANY_HIT = 0, 1
 
 
+class Point(C.Structure):
+    """bm_point: one point of bm_scene_closest_points (16 bytes)."""
+    _fields_ = [("p", C.c_float * 3), ("rmax", C.c_float)]
+
+
 class AttrReq(C.Structure):
     """bm_attr_req: one request of bm_scene_hit_attributes (24 bytes)."""
     _fields_ = [("slot", C.c_uint32), ("components", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32),
@@ -166,6 +171,8 @@ SIGNATURES = {
     "bm_scene_destroy": (None, [_P]),
     "bm_scene_trace_rays": (_I, [_P, _P, _U, _U, _U, _P]),
     "bm_scene_trace_rays_counters": (_I, [_P, _P, _U, _U, _U, _P, _U64P]),
+    "bm_scene_closest_points": (_I, [_P, _P, _U, _U, _P]),
+    "bm_scene_closest_points_counters": (_I, [_P, _P, _U, _U, _P, _U64P]),
     "bm_scene_hit_attributes": (_I, [_P, _P, _U, C.POINTER(AttrReq), _U]),
     "bm_camera_create": (_I, [_P, C.POINTER(_P)]),
     "bm_camera_set_initial_rays": (_I, [_P, _U, _U, _F, _F, _F, _F, _F]),

@@ -417,6 +417,68 @@ class IScene:
             res["counters"] = cnt
         return res
 
+    def closestPointsDevice(self, points_ptr: int, n: int, out_ptr: int, counters=None, flags=0) -> int:
+        """bm_scene_closest_points on device pointers (n bm_point records of 16 bytes in, n bm_hit records of
+        16 bytes out, both 16-byte aligned); returns the error code. Asynchronous on the context stream unless
+        `counters` (a uint64[4] numpy array to fill) is given. flags: none defined yet."""
+        pp, op = C.c_void_p(points_ptr or None), C.c_void_p(out_ptr or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_closest_points(self.h, pp, n, flags, op)
+        return self.ctx.lib.bm_scene_closest_points_counters(self.h, pp, n, flags, op,
+                                                             counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def closestPoints(self, points, rmax=None, counters: bool = False):
+        """The nearest triangle to each of n points (bm_scene_closest_points): its distance t, the
+        barycentrics u, v of the closest point and its global id. rmax: None (unbounded), a scalar or n
+        values; a point with no triangle within rmax gets the miss record (t = inf, tri_id = NO_TRIANGLE).
+
+        numpy (n,3) float32 points: packs, uploads, queries and waits; returns numpy arrays
+        {"t", "u", "v", "tri_id"}.
+        torch tensors on the context's device — points (n,3) with rmax None, a scalar or an (n,) tensor, or
+        one packed (n,4) float32 tensor (p, rmax): everything stays on the device and nothing waits. Returns
+        {"hits": (n,4) float32, "t", "u", "v", "tri_id"} with the views traceRays returns; "hits" goes straight
+        into hitAttributes, where VERTEX_DATA_POSITION is the closest point itself. Make the context on
+        torch's stream, as for traceRays.
+        counters=True adds "counters": [node records, triangle evaluations, points with a result, deepest
+        stack] (waits)."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        on_device = isinstance(points, torch.Tensor)
+        if on_device:
+            if points.dim() == 2 and points.shape[1] == 4 and rmax is None:
+                pts = points
+            elif points.dim() == 2 and points.shape[1] == 3:
+                pts = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+                pts[:, 0:3] = points
+                pts[:, 3] = float("inf") if rmax is None else rmax
+            else:
+                raise BeamError(ERROR_INVALID_PARAMETER, "closestPoints: points are (n, 3), or packed (n, 4), float32")
+            if pts.device != dev or pts.dtype != torch.float32 or not pts.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"closestPoints: points must be contiguous float32 on {dev} (the context's device)")
+        else:
+            q = _f32(points).reshape(-1, 3)
+            packed = np.zeros((q.shape[0], 4), np.float32)
+            packed[:, 0:3] = q
+            packed[:, 3] = np.inf if rmax is None else rmax
+            pts = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = pts.shape[0]
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        cnt = np.zeros(4, np.uint64) if counters else None
+        self.ctx._check(self.closestPointsDevice(pts.data_ptr() if n else 0, n, out.data_ptr() if n else 0, cnt))
+        self._points_keep = pts  # until the next query: the kernel may not have read them yet
+        if on_device:
+            res = {"hits": out, "t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "tri_id": out.view(torch.int32)[:, 3]}
+        else:
+            self.ctx.sync()
+            h = out.cpu().numpy()
+            res = {"t": h[:, 0].copy(), "u": h[:, 1].copy(), "v": h[:, 2].copy(),
+                   "tri_id": h.view(np.uint32)[:, 3].copy()}
+        if counters:
+            res["counters"] = cnt
+        return res
+
     def hitAttributesDevice(self, hits_ptr: int, n: int, requests) -> int:
         """bm_scene_hit_attributes on device pointers: n bm_hit records of 16 bytes in, and per request
         (slot, components, flags, out_ptr[, pad]) n rows of `components` 4-byte words out, every pointer

@@ -45,7 +45,7 @@ struct bm_context {
     uint32_t bvh_width = 4;     // BM_OPT_BVH2 -> 2
     void* ovf = nullptr;  // traversal-stack overflow area of the persistent trace grid
     size_t ovf_cap = 0;
-    unsigned long long* rays_counters = nullptr;  // ray queries: the counting form's three counters
+    unsigned long long* rays_counters = nullptr;  // ray and closest-point queries: the counting forms' counters (4)
     unsigned long long* tile_ctr = nullptr;  // ticket counter of the dynamic trace variants
     unsigned long long tile_base = 0;        // its value at the next launch
     // render targets with their own stream (bm_rt_set_stream): traces into them run there, ordered
@@ -1878,22 +1878,27 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
     return BM_ERROR_ALL_FINE;
 }
 
-// ---- ray queries (bm_rays.hip) -------------------------------------------------------------------
-static int32_t rays_impl(bm_scene* s, const bm_ray* rays, uint32_t n, uint32_t mode, uint32_t flags, void* out,
-                         uint64_t* counters) {
+// ---- queries over a caller's batch: rays (bm_rays.hip) and points (bm_points.hip) ----------------
+// One path for both: the checks in the order beam_c.h lists them, the quad kernels' launch parameters on the
+// context stream with the overflow area reserved, the launch, and for the counting forms the counters read
+// back (3 words for rays, 4 for points; synchronous). points: a closest-point query (mode is not read).
+static int32_t query_impl(bm_scene* s, bool points, const void* in, uint32_t n, uint32_t mode, uint32_t flags,
+                          void* out, uint64_t* counters) {
     if (!s) return BM_ERROR_INVALID_PARAMETER;
     bm_context* ctx = s->ctx;
-    if (n && (!rays || !out)) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: null ray or result pointer");
-    if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u)
-        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: ray and result pointers must be 16-byte aligned");
-    if (mode > BM_RAYS_ANY_HIT || flags != 0)  // no flag bits are defined
-        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: unknown mode or flag bits");
+    const std::string who = points ? "closest_points: " : "trace_rays: ";
+    if (n && (!in || !out)) return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "null input or result pointer");
+    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "input and result pointers must be 16-byte aligned");
+    if ((!points && mode > BM_RAYS_ANY_HIT) || flags != 0)  // no flag bits are defined
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "unknown mode or flag bits");
     if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
-        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
     if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
     if (s->kd || s->hash || s->width != 4)
-        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "trace_rays: BVH4 scenes only (no reference mode, BVH2 or BVH8)");
-    if (counters) counters[0] = counters[1] = counters[2] = 0;
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    const int words = points ? 4 : 3;
+    if (counters) std::fill(counters, counters + words, uint64_t(0));
     if (n == 0) return BM_ERROR_ALL_FINE;
     BM_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
@@ -1905,34 +1910,45 @@ static int32_t rays_impl(bm_scene* s, const bm_ray* rays, uint32_t n, uint32_t m
     p.bvh_width = 4;
     p.prio_after = ctx->prio_after;
     p.prio_level = ctx->prio_level;
-    p.q_rays = reinterpret_cast<const float4*>(rays);
+    p.q_rays = reinterpret_cast<const float4*>(in);
     p.q_out = out;
     p.q_n = n;
     if (const int32_t e = reserve_overflow(ctx, nullptr, st, p)) return e;
     if (counters) {
-        if (!ctx->rays_counters) BM_HIP(ctx, hipMalloc(&ctx->rays_counters, 3 * sizeof(unsigned long long)));
-        BM_HIP(ctx, hipMemsetAsync(ctx->rays_counters, 0, 3 * sizeof(unsigned long long), st));
+        if (!ctx->rays_counters) BM_HIP(ctx, hipMalloc(&ctx->rays_counters, 4 * sizeof(unsigned long long)));
+        BM_HIP(ctx, hipMemsetAsync(ctx->rays_counters, 0, 4 * sizeof(unsigned long long), st));
         p.counters = ctx->rays_counters;
     }
-    BM_HIP(ctx, bm::launch_query_rays(p, mode, counters != nullptr, st));
+    BM_HIP(ctx, points ? bm::launch_closest_points(p, counters != nullptr, st)
+                       : bm::launch_query_rays(p, mode, counters != nullptr, st));
     if (counters) {
-        unsigned long long h[3];
+        unsigned long long h[4];
         BM_HIP(ctx, hipMemcpyAsync(h, ctx->rays_counters, sizeof(h), hipMemcpyDeviceToHost, st));
         BM_HIP(ctx, hipStreamSynchronize(st));
-        for (int i = 0; i < 3; ++i) counters[i] = h[i];
+        std::copy(h, h + words, counters);
     }
     return BM_ERROR_ALL_FINE;
 }
 
 int32_t bm_scene_trace_rays(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode, uint32_t flags,
                             void* out_dev) {
-    return rays_impl(s, rays_dev, n, mode, flags, out_dev, nullptr);
+    return query_impl(s, false, rays_dev, n, mode, flags, out_dev, nullptr);
 }
 
 int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode, uint32_t flags,
                                      void* out_dev, uint64_t out[3]) {
     if (!out) return BM_ERROR_INVALID_PARAMETER;
-    return rays_impl(s, rays_dev, n, mode, flags, out_dev, out);
+    return query_impl(s, false, rays_dev, n, mode, flags, out_dev, out);
+}
+
+int32_t bm_scene_closest_points(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t flags, bm_hit* out_dev) {
+    return query_impl(s, true, points_dev, n, 0, flags, out_dev, nullptr);
+}
+
+int32_t bm_scene_closest_points_counters(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t flags,
+                                         bm_hit* out_dev, uint64_t out[4]) {
+    if (!out) return BM_ERROR_INVALID_PARAMETER;
+    return query_impl(s, true, points_dev, n, 0, flags, out_dev, out);
 }
 
 // ---- hit attributes (bm_attrs.hip) ---------------------------------------------------------------

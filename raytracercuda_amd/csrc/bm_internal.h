@@ -185,7 +185,8 @@ struct TraceParams {
     uint32_t rayq_region, rayq_tpr, rayq_regions;
     uint32_t fast_cull;  // orient is near-orthonormal: k_cull may use approximate ray setup
     // ray queries (bm_rays.hip): q_n caller rays of two float4 each, (origin, tmax) (dir, pad); q_out one
-    // bm_hit (closest) or one byte (any hit) per ray
+    // bm_hit (closest) or one byte (any hit) per ray. Closest-point queries (bm_points.hip): q_n points of
+    // one float4 each, (p, rmax); q_out one bm_hit per point
     const float4* q_rays;
     void* q_out;
     uint32_t q_n;
@@ -216,6 +217,10 @@ hipError_t launch_shadow(const TraceParams& p, bool count, hipStream_t s);
 // Ray query (bm_rays.hip): BM_RAYS_CLOSEST or BM_RAYS_ANY_HIT over p.q_rays on a BVH4 scene, ray quads on
 // the persistent grid with the overflow area set up as for launch_trace; count: into p.counters.
 hipError_t launch_query_rays(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
+// Closest-point query (bm_points.hip): the nearest triangle to each of p.q_n points, one float4 (p, rmax) each
+// in p.q_rays, one bm_hit each into p.q_out; BVH4 scenes, set up as for launch_query_rays. count: into
+// p.counters[0..3] (node records, triangle evaluations, points with a result, the deepest stack held).
+hipError_t launch_closest_points(const TraceParams& p, bool count, hipStream_t s);
 // ---- hit attributes (bm_attrs.hip): vertex slots interpolated at the hits of a ray query ------------
 // One entry per scene mesh, in scene order: every slot's device buffer (null: the mesh has none), so the
 // table depends on the meshes alone and not on what a call requests.
