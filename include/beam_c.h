@@ -230,7 +230,9 @@ int32_t bm_context_start_comm(bm_context* ctx, int32_t rank, int32_t size, const
                                          reports BM_ERROR_GPU_ALLOC_FAIL */
 #define BM_PARAM_TRACE_AUTO_PACKET 24 /* 0: never switch dense coherent views to wave packets (BM_PARAM_TRACE_VARIANT 14) */
 #define BM_PARAM_KD_TOP_RANK 25 /* 0: reference-mode pair sort in four plain passes (no ranked top digit; A/B) */
-#define BM_PARAM_COUNT 26
+#define BM_PARAM_CULL_DEPTH 26 /* compacted trace: record levels k_cull culls by (1, the default: the root record;
+                                * 2: the root's entered child records too — fewer queued rays, measured slower) */
+#define BM_PARAM_COUNT 27
 int32_t bm_context_set_param(bm_context* ctx, uint32_t key, int64_t value);
 /* The value set for key, -1 while the library default is in effect; INT64_MIN for an unknown key. */
 int64_t bm_context_get_param(const bm_context* ctx, uint32_t key);
@@ -578,6 +580,11 @@ void* bm_rt_stream(const bm_rt* rt);
 #define BM_TRACE_KIND_HASH_MARCH 4  /* hashed-grid mode: k_hash_march */
 #define BM_TRACE_KIND_PACKETS 5     /* k_trace_packet (BM_PARAM_TRACE_VARIANT 14: wave packets) */
 int32_t bm_rt_trace_kind(const bm_rt* rt);
+/* Measurement: the ray queue of the last trace into this target, when that trace was compacted
+ * (BM_TRACE_KIND_CULL_QUADS; BM_ERROR_NOT_BUILT otherwise). *regions = its queue regions; out receives the
+ * first min(capacity, *regions) region counts — the rays per region that survived k_cull and were traced
+ * as quads (their sum: the queue's rays; k_trace_rays walks ceil(sum / 16) batches). Synchronous. */
+int32_t bm_rt_ray_queue_counts(bm_rt* rt, uint32_t* out, uint32_t capacity, uint32_t* regions);
 /* Multi-device contexts: the device-time split of the last frame traced into this (root) target,
  * from HIP events on the streams it ran on: out_ms[0] = this process's band trace (its first band
  * source), out_ms[1] = the exchange after it (RCCL send/recv or peer writes, band scatter and

@@ -114,7 +114,7 @@ PARAMS = {"trace_variant": 0, "trace_sched": 1, "trace_scramble": 2, "trace_prio
           "kd_queue_cap": 10, "kd_lq_cap": 11, "kd_split": 12, "kd_grid": 13, "kd_pair": 14, "kd_tb": 15,
           "kd_march": 16, "msd_max_n": 17, "nrm_defer": 18, "bucket_lds_cap": 19, "msd_wide_n": 20,
           "front_max_n": 21, "orig_lazy": 22, "kd_max_leaves": 23,
-          "trace_auto_packet": 24, "kd_top_rank": 25}
+          "trace_auto_packet": 24, "kd_top_rank": 25, "cull_depth": 26}
 
 
 _P = C.c_void_p
@@ -141,6 +141,7 @@ SIGNATURES = {
     "bm_context_set_param": (_I, [_P, _U, C.c_int64]),
     "bm_context_get_param": (C.c_int64, [_P, _U]),
     "bm_rt_last_timing": (_I, [_P, _FP]),
+    "bm_rt_ray_queue_counts": (_I, [_P, _UP, _U, _UP]),
     "bm_mesh_create": (_I, [_P, C.POINTER(_P)]),
     "bm_mesh_set_vertex_data": (_I, [_P, _FP, _U, _U, _U]),
     "bm_mesh_set_indices": (_I, [_P, _UP, _U]),

@@ -636,6 +636,16 @@ class IRenderTarget:
         """Kernels the last trace into this target ran (bm_rt_trace_kind): quads, cull+quads, ..."""
         return self.TRACE_KINDS.get(int(self.ctx.lib.bm_rt_trace_kind(self.h)), "none")
 
+    def rayQueueCounts(self):
+        """Rays per queue region that survived k_cull in the last trace into this target, a uint32 array
+        (bm_rt_ray_queue_counts; that trace must have been compacted: traceKind() 'cull+quads')."""
+        n = C.c_uint32(0)
+        self.ctx._check(self.ctx.lib.bm_rt_ray_queue_counts(self.h, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint32)
+        if n.value:
+            self.ctx._check(self.ctx.lib.bm_rt_ray_queue_counts(self.h, _up(out), n.value, C.byref(n)))
+        return out
+
     def lastTiming(self):
         """Multi-device contexts: (band trace ms, exchange ms) of the last frame traced into this
         target, from HIP events (bm_rt_last_timing; waits for that frame)."""

@@ -221,9 +221,10 @@ struct bm_rt {
     DevBuf shadow;  // u8 plane (width x height), allocated by the first shadow trace
     DevBuf queue;   // shadow-pass queue: count word, then up to width x height pixel indices
     DevBuf rayq;    // compacted trace: region counts, then the regions' ray entries
+    uint32_t rayq_regions = 0;  // region counts the last compacted trace wrote (bm_rt_ray_queue_counts)
     DevBuf tile_cost;  // cost-ordered schedule (sched 2): last trace's time per quad-kernel tile
     hipStream_t stream = nullptr;  // bm_rt_set_stream; null: the context stream
-    hipEvent_t done = nullptr;     // recorded after each trace on `stream`
+    hipEvent_t done = nullptr;     // recorded on `stream` by ctx_drain, just before the context stream waits for it
     uint64_t epoch = 0;            // context epoch this target's stream last synchronised with
     DevBuf ovf;                    // traversal-stack overflow area of traces on `stream`
     int32_t last_kind = -1;        // BM_TRACE_KIND_* of the last trace into this target
@@ -245,9 +246,12 @@ hipStream_t rt_stream(const bm_rt* rt) { return rt->stream ? rt->stream : rt->ct
 
 // Context-stream work that traces read (builds, ray tables) is about to change: wait (on the
 // device) for the last trace of every render target with its own stream, and open a new epoch.
+// The event is recorded here, where it is waited for, and not after every trace: one stream packet
+// fewer per frame, and the record covers whatever the target's stream holds by now.
 hipError_t ctx_drain(bm_context* ctx) {
     for (bm_rt* r : ctx->rt_streams) {
-        hipError_t e = hipStreamWaitEvent(ctx->stream, r->done, 0);
+        hipError_t e = hipEventRecord(r->done, r->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, r->done, 0);
         if (e != hipSuccess) return e;
     }
     ++ctx->epoch;
@@ -554,6 +558,8 @@ int32_t bm_context_set_param(bm_context* ctx, uint32_t key, int64_t value) {
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: KD_TB is 64 or 256");
     if (key == BM_PARAM_KD_MARCH && value > 3) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: KD_MARCH 0..3");
     if (key == BM_PARAM_TRACE_PRIO_LEVEL && value > 3) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: prio 0..3");
+    if (key == BM_PARAM_CULL_DEPTH && (value == 0 || value > 2))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: CULL_DEPTH is 1 or 2");
     // k_front (one-launch gather + keys + top-digit pass) was removed in round 5
     if (key == BM_PARAM_FRONT_MAX_N && value > 0)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: FRONT_MAX_N: k_front was removed (always 0)");
@@ -1734,7 +1740,6 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
             k.cnodes = s->kd_cnodes_valid ? s->kd_cnodes.as<const uint4>() : nullptr;
             BM_HIP(ctx, bm::launch_kd_march(p, k, rq.count, st));
         }
-        if (rt->stream) BM_HIP(ctx, hipEventRecord(rt->done, st));
         return BM_ERROR_ALL_FINE;
     }
     bm::TraceParams p{};
@@ -1843,6 +1848,8 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
                 worst = std::max(worst, std::fabs(d - (i == j ? 1.0 : 0.0)));
             }
         p.fast_cull = worst < 0x1p-10 ? 1u : 0u;
+        p.cull_depth = (uint32_t)ctx->tune.get(BM_PARAM_CULL_DEPTH, 1);  // 2 measured slower on C3
+        rt->rayq_regions = regions;
         p.rayq_region = (uint32_t)region;
         p.rayq_tpr = tpr;
         p.rayq_regions = regions;
@@ -1874,7 +1881,6 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
     if (rq.grid_out) *rq.grid_out = grid;
     if (dyn) ctx->tile_base += (unsigned long long)((p.width + 7) / 8) * ((p.local_rows + 7) / 8) + 4ull * grid;
     if (shadow) BM_HIP(ctx, bm::launch_shadow(p, rq.count, st));
-    if (rt->stream) BM_HIP(ctx, hipEventRecord(rt->done, st));
     return BM_ERROR_ALL_FINE;
 }
 
@@ -2298,7 +2304,6 @@ static int32_t trace_multi(bm_camera* c, const float* eye3, const float* orient3
     }
     BM_HIP(ctx, hipEventRecord(rt->mg_t[2], st));
     rt->mg_timed = true;
-    if (rt->stream) BM_HIP(ctx, hipEventRecord(rt->done, st));
     return BM_ERROR_ALL_FINE;
 }
 
@@ -2584,6 +2589,21 @@ int32_t bm_rt_set_stream(bm_rt* rt, void* stream) {
 void* bm_rt_stream(const bm_rt* rt) { return rt ? reinterpret_cast<void*>(rt_stream(rt)) : nullptr; }
 
 int32_t bm_rt_trace_kind(const bm_rt* rt) { return rt ? rt->last_kind : -1; }
+
+int32_t bm_rt_ray_queue_counts(bm_rt* rt, uint32_t* out, uint32_t capacity, uint32_t* regions) {
+    if (!rt || !regions || (capacity && !out)) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = rt->ctx;
+    if (rt->last_kind != BM_TRACE_KIND_CULL_QUADS || !rt->rayq.p)
+        return fail(ctx, BM_ERROR_NOT_BUILT, "ray_queue_counts: the last trace into this target was not compacted");
+    *regions = rt->rayq_regions;
+    const uint32_t n = std::min(capacity, rt->rayq_regions);
+    if (!n) return BM_ERROR_ALL_FINE;
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = rt_stream(rt);
+    BM_HIP(ctx, hipMemcpyAsync(out, rt->rayq.p, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
+    BM_HIP(ctx, hipStreamSynchronize(st));
+    return BM_ERROR_ALL_FINE;
+}
 
 int32_t bm_rt_save_ppm(bm_rt* rt, const char* path) {
     if (!rt || !path) return BM_ERROR_INVALID_PARAMETER;

@@ -184,6 +184,7 @@ struct TraceParams {
     uint32_t* rayq_count;
     uint32_t rayq_region, rayq_tpr, rayq_regions;
     uint32_t fast_cull;  // orient is near-orthonormal: k_cull may use approximate ray setup
+    uint32_t cull_depth;  // 1: k_cull tests the root record; 2: the entered child records too (BM_PARAM_CULL_DEPTH)
     // ray queries (bm_rays.hip): q_n caller rays of two float4 each, (origin, tmax) (dir, pad); q_out one
     // bm_hit (closest) or one byte (any hit) per ray. Closest-point queries (bm_points.hip): q_n points of
     // one float4 each, (p, rmax); q_out one bm_hit per point

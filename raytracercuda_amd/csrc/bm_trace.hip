@@ -129,7 +129,8 @@ hipError_t launch_variant(const TraceParams& p, int variant, hipStream_t s, uint
         case TRACE_COMPACT:
             if constexpr (W == 4 && SH != SH_QUEUE) {
                 if (p.rayq) {  // the host sized the ray queue (trace_compact_layout)
-                    k_cull<COUNT, SH><<<p.rayq_regions, BLOCK, 0, s>>>(p);
+                    if (!COUNT && p.cull_depth >= 2) k_cull_deep<SH><<<p.rayq_regions, BLOCK, 0, s>>>(p);
+                    else k_cull<COUNT, SH><<<p.rayq_regions, BLOCK, 0, s>>>(p);
                     if (COUNT && p.diag) launch_persistent(k_trace_rays<true, QUAD_LDS, 1, SH, true>, p, s, grid);
                     else if (p.prio_after == 0) launch_persistent(k_trace_rays<COUNT, QUAD_LDS, 0, SH>, p, s, grid);
                     else launch_persistent(k_trace_rays<COUNT, QUAD_LDS, 1, SH>, p, s, grid);
