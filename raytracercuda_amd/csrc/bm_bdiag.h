@@ -2,6 +2,11 @@
 // Included inside `namespace bm { namespace {` of each translation unit that times its build kernels
 // (bm_build.hip: the LBVH build, kernel rows 0..8; bm_kd.hip: the reference-mode kd build, rows 9..15),
 // so each has its own slot buffer; bm_debug_build_diag merges their rows.
+// The marker of a device function that takes one, where nothing is timed (every build's LSD fallback
+// inside k_bucket_sort; every kernel of a build without BM_BUILD_DIAG)
+struct NoDiag {
+    __device__ void mark(int) const {}
+};
 #ifdef BM_BUILD_DIAG
 // Every wave of a build kernel stores its start and end (s_memrealtime, 100 MHz) into its own slot of
 // g_bdiag (no shared words: no contention to distort the times), so that the host can place each
@@ -37,6 +42,7 @@ struct BDiag {
 };
 #define BDIAG(k) BDiag bdiag_scope_(k)
 #define BDIAG_MARK(i) bdiag_scope_.mark(i)
+#define BDIAG_OBJ bdiag_scope_  // the kernel's BDiag, for device functions that take their marker as an argument
 
 // out == nullptr zeroes this unit's slots (allocated on first use); otherwise copies kernel rows
 // [k0, k1) of them to the same rows of out (BDIAG_KERNELS * BDIAG_WAVES * BDIAG_WORDS u64).
@@ -55,4 +61,5 @@ static hipError_t bdiag_io(const void* sym, unsigned long long* out, uint32_t k0
 #else
 #define BDIAG(k)
 #define BDIAG_MARK(i)
+#define BDIAG_OBJ NoDiag()
 #endif

@@ -76,89 +76,13 @@ __device__ __forceinline__ bool axis_sep(float pa, float pb, float rad) {
 }
 
 // triBoxOverlap (BoxTriangle.cuh:134-222): the nine cross-axis tests (AXISTEST_* order), the AABB
-// test (FINDMINMAX) and the plane test, operation for operation.
-__device__ bool tri_box_branchy(const float* bc, const float* hs, const float* tv) {
-    float v0[3], v1[3], v2[3], e0[3], e1[3], e2[3], nrm[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        v0[c] = tv[c] - bc[c];
-        v1[c] = tv[3 + c] - bc[c];
-        v2[c] = tv[6 + c] - bc[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        e0[c] = v1[c] - v0[c];
-        e1[c] = v2[c] - v1[c];
-        e2[c] = v0[c] - v2[c];
-    }
-    float fx, fy, fz, a, b, pa, pb, rad;
-    fx = fabsf(e0[0]); fy = fabsf(e0[1]); fz = fabsf(e0[2]);
-    a = e0[2]; b = e0[1];
-    pa = a * v0[1] - b * v0[2]; pb = a * v2[1] - b * v2[2];
-    rad = fz * hs[1] + fy * hs[2];
-    if (axis_sep(pa, pb, rad)) return false;
-    a = e0[2]; b = e0[0];
-    pa = -a * v0[0] + b * v0[2]; pb = -a * v2[0] + b * v2[2];
-    rad = fz * hs[0] + fx * hs[2];
-    if (axis_sep(pa, pb, rad)) return false;
-    a = e0[1]; b = e0[0];
-    pa = a * v1[0] - b * v1[1]; pb = a * v2[0] - b * v2[1];
-    rad = fy * hs[0] + fx * hs[1];
-    if (axis_sep(pb, pa, rad)) return false;
-
-    fx = fabsf(e1[0]); fy = fabsf(e1[1]); fz = fabsf(e1[2]);
-    a = e1[2]; b = e1[1];
-    pa = a * v0[1] - b * v0[2]; pb = a * v2[1] - b * v2[2];
-    rad = fz * hs[1] + fy * hs[2];
-    if (axis_sep(pa, pb, rad)) return false;
-    a = e1[2]; b = e1[0];
-    pa = -a * v0[0] + b * v0[2]; pb = -a * v2[0] + b * v2[2];
-    rad = fz * hs[0] + fx * hs[2];
-    if (axis_sep(pa, pb, rad)) return false;
-    a = e1[1]; b = e1[0];
-    pa = a * v0[0] - b * v0[1]; pb = a * v1[0] - b * v1[1];
-    rad = fy * hs[0] + fx * hs[1];
-    if (axis_sep(pa, pb, rad)) return false;
-
-    fx = fabsf(e2[0]); fy = fabsf(e2[1]); fz = fabsf(e2[2]);
-    a = e2[2]; b = e2[1];
-    pa = a * v0[1] - b * v0[2]; pb = a * v1[1] - b * v1[2];
-    rad = fz * hs[1] + fy * hs[2];
-    if (axis_sep(pa, pb, rad)) return false;
-    a = e2[2]; b = e2[0];
-    pa = -a * v0[0] + b * v0[2]; pb = -a * v1[0] + b * v1[2];
-    rad = fz * hs[0] + fx * hs[2];
-    if (axis_sep(pa, pb, rad)) return false;
-    a = e2[1]; b = e2[0];
-    pa = a * v1[0] - b * v1[1]; pb = a * v2[0] - b * v2[1];
-    rad = fy * hs[0] + fx * hs[1];
-    if (axis_sep(pb, pa, rad)) return false;
-
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float mn = v0[c], mx = v0[c];
-        if (v1[c] < mn) mn = v1[c];
-        if (v1[c] > mx) mx = v1[c];
-        if (v2[c] < mn) mn = v2[c];
-        if (v2[c] > mx) mx = v2[c];
-        if (mn > hs[c] || mx < -hs[c]) return false;
-    }
-    nrm[0] = e0[1] * e1[2] - e0[2] * e1[1];
-    nrm[1] = e0[2] * e1[0] - e0[0] * e1[2];
-    nrm[2] = e0[0] * e1[1] - e0[1] * e1[0];
-    return plane_box(nrm, v0, hs);
-}
-
-// The same tests without the early returns: every test's arithmetic is the one above (same operands,
-// same order, no contraction), and the reference's function has no side effects, so "false at the
-// first separating test, else the plane test" equals "no test separates, and the plane test passes".
-// Straight-line code: a wave whose lanes separate at different tests no longer runs the union of
-// the return paths with their exec-mask saves (the descent walks ran at ~5k cycles per level with
-// the branches; -DBM_KD_SAT_FLAT=0 restores them for an A/B).
-#ifndef BM_KD_SAT_FLAT
-#define BM_KD_SAT_FLAT 1
-#endif
-// The test groups of tri_box_flat, each with the operations above (same operands, same order).
+// test (FINDMINMAX) and the plane test, operation for operation (same operands, same order, no
+// contraction) but without the reference's early returns: its function has no side effects, so "false
+// at the first separating test, else the plane test" equals "no test separates, and the plane test
+// passes". Straight-line code: a wave whose lanes separate at different tests does not run the union
+// of the return paths with their exec-mask saves (the descent walks ran at ~5k cycles per level with
+// the branches).
+// The test groups of tri_box, each with the reference's operations.
 struct SatFrame {
     float v0[3], v1[3], v2[3], e0[3], e1[3], e2[3];
 };
@@ -257,13 +181,13 @@ __device__ __forceinline__ bool sat_plane(const SatFrame& f, const float* hs) {
     nrm[2] = f.e0[0] * f.e1[1] - f.e0[1] * f.e1[0];
     return plane_box(nrm, f.v0, hs);
 }
-__device__ __forceinline__ bool tri_box_flat(const float* bc, const float* hs, const float* tv) {
+__device__ __forceinline__ bool tri_box(const float* bc, const float* hs, const float* tv) {
     SatFrame f;
     sat_frame(bc, tv, f);
     const bool sep = sat_sep_e0(f, hs) | sat_sep_e1(f, hs) | sat_sep_e2(f, hs) | sat_sep_box(f, hs);
     return !sep && sat_plane(f, hs);
 }
-// tri_box_flat's tests split over two lanes (round 6): half 0 the cross-axis tests of edges e0 and e1,
+// tri_box's tests split over two lanes (round 6): half 0 the cross-axis tests of edges e0 and e1,
 // half 1 those of e2, the AABB test and the plane test. Every test is the one above, and the function
 // is "no test separates and the plane test passes", so (half 0's result) && (half 1's) is its result.
 __device__ __forceinline__ bool tri_box_half(const float* bc, const float* hs, const float* tv, bool half) {
@@ -273,10 +197,10 @@ __device__ __forceinline__ bool tri_box_half(const float* bc, const float* hs, c
     return !(sat_sep_e2(f, hs) | sat_sep_box(f, hs)) && sat_plane(f, hs);
 }
 
-// tri_box_flat for a triangle whose coordinates are all below 2^60 in magnitude (kd_finite; the walks' boxes
+// tri_box for a triangle whose coordinates are all below 2^60 in magnitude (kd_finite; the walks' boxes
 // lie in the world box): every intermediate is then finite — |v| < 2^61, |e| < 2^62, each product below
 // 2^124 — and for finite operands "a < b ? a : b" and fminf differ at most in the sign of a zero, which no
-// comparison sees, so the min/max forms below give tri_box_flat's answer with fewer instructions (round 6).
+// comparison sees, so the min/max forms below give tri_box's answer with fewer instructions (round 6).
 __device__ __forceinline__ bool axis_sep_finite(float pa, float pb, float rad) {
     return fminf(pa, pb) > rad || fmaxf(pa, pb) < -rad;
 }
@@ -286,7 +210,7 @@ __device__ __forceinline__ bool tri_box_finite(const float* bc, const float* hs,
     const float* v0 = f.v0; const float* v1 = f.v1; const float* v2 = f.v2;
     bool sep = false;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {  // edges e0, e1, e2: AXISTEST_X, _Y, _Z with tri_box_flat's vertex pairs
+    for (int q = 0; q < 3; ++q) {  // edges e0, e1, e2: AXISTEST_X, _Y, _Z with tri_box's vertex pairs
         const float* e = q == 0 ? f.e0 : q == 1 ? f.e1 : f.e2;
         const float* xa = q == 2 ? v0 : v0;
         const float* xb = q == 2 ? v1 : v2;
@@ -315,48 +239,9 @@ __device__ __forceinline__ bool kd_finite(const float* tv) {
     return ok;
 }
 
-__device__ __forceinline__ bool tri_box(const float* bc, const float* hs, const float* tv) {
-    return BM_KD_SAT_FLAT ? tri_box_flat(bc, hs, tv) : tri_box_branchy(bc, hs, tv);
-}
-
-// Exact shortcuts to triBoxOverlap, an A/B experiment (-DBM_KD_SAT_SHORTCUT=1; measured slower,
-// DESIGN.md §8): the result equals tri_box for every input.
-//  * false when the test's own AABB step separates: tri_box computes v_i = tv_i - bc first and returns
-//    false at a cross-axis test or at this step, so the step's verdict (same operations) decides;
-//  * true when every |v_i[c]| <= hs[c] (1 - 2^-20): then no test can separate. A cross-axis test
-//    compares p = a v[j] - b v[k] with rad = |a| hs[j] + |b| hs[k] (a, b: one edge's components): in
-//    float |p| <= (|a||v[j]| + |b||v[k]|)(1 + u)^2 and rad >= (|a| hs[j] + |b| hs[k])(1 - u)^2 (u = 2^-24,
-//    nonnegative terms), so the 16u margin keeps |p| <= rad; the AABB step passes outright; and the plane
-//    test's dot products sum terms n[q] * (+-hs[q] - v0[q]) whose factors' signs are exact (hs - |v0| >
-//    0 stays nonzero under rounding), all <= 0 for vmin and >= 0 for vmax, so it returns true. The bound
-//    is relative: edge components must be 0 or at least 2^-100 (no subnormal products against a
-//    normal rad), and hs >= 2^-60.
-#ifndef BM_KD_SAT_SHORTCUT
-#define BM_KD_SAT_SHORTCUT 0
-#endif
-__device__ __forceinline__ bool normal_or_zero(float e) { return e == 0.0f || fabsf(e) >= 0x1p-100f; }
-#ifndef BM_KD_SAT_FINITE
-#define BM_KD_SAT_FINITE 1
-#endif
+// tri_box, by tri_box_finite when the caller showed the triangle qualifies (fin = kd_finite(tv))
 __device__ __forceinline__ bool tri_box_fast(const float* bc, const float* hs, const float* tv, bool fin = false) {
-    if (BM_KD_SAT_FINITE && fin) return tri_box_finite(bc, hs, tv);
-    if (!BM_KD_SAT_SHORTCUT) return tri_box(bc, hs, tv);
-    bool sep = false, inside = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float a = tv[c] - bc[c], b = tv[3 + c] - bc[c], d = tv[6 + c] - bc[c];
-        float mn = a, mx = a;  // FINDMINMAX order (tri_box)
-        if (b < mn) mn = b;
-        if (b > mx) mx = b;
-        if (d < mn) mn = d;
-        if (d > mx) mx = d;
-        sep = sep || mn > hs[c] || mx < -hs[c];
-        const float lim = hs[c] * (1.0f - 0x1p-20f);
-        inside = inside && hs[c] >= 0x1p-60f && fabsf(a) <= lim && fabsf(b) <= lim && fabsf(d) <= lim &&
-                 normal_or_zero(b - a) && normal_or_zero(d - b) && normal_or_zero(a - d);
-    }
-    if (sep) return false;
-    if (inside) return true;
+    if (fin) return tri_box_finite(bc, hs, tv);
     return tri_box(bc, hs, tv);
 }
 
@@ -578,7 +463,7 @@ struct KdSplitArgs {
     uint32_t zero_words;
     uint32_t* topmap;         // count pass: map of the queued nodes' top 11 path bits (KdBuild::topmap)
     uint32_t* topcount;       // and the number of its bits set
-    uint32_t copy_first;      // emit pass: k_kd_sub's workgroups from this index do k_kd_copy's work (0: none)
+    uint32_t copy_first;      // emit pass: k_kd_sub's workgroups from this index copy the cached leaves (0: none)
 };
 
 // GRID (a.grid_exact, decided at launch): the closed form; else the halving recurrence, unrolled
@@ -631,11 +516,8 @@ __device__ __forceinline__ int pair_swap(int v) {
 // combine by a lane swap inside the pair, the children's by a swap between the pairs. The node visits, tests
 // and leaves are the two-lane walk's (GPU tests green with it), but the halves are different code, so a wave
 // runs both one after the other: measured slower (bunny kd build 0.32 -> 0.36 ms, merged 1.28 -> 1.88 ms),
-// an A/B define only.
-#ifndef BM_KD_WALK_LANES
-#define BM_KD_WALK_LANES 2
-#endif
-constexpr uint32_t KD_PW = BM_KD_WALK_LANES;
+// so the product walks with 2.
+constexpr uint32_t KD_PW = 2;
 static_assert(KD_PW == 2 || KD_PW == 4, "lanes per walk: 2 or 4");
 template <bool PAIR>
 constexpr uint32_t kd_w() { return PAIR ? KD_PW : 1u; }
@@ -770,9 +652,6 @@ __device__ __forceinline__ void kd_walk(const KdSplitArgs& a, uint32_t g, const 
 // slot, node) entry and walks it with that triangle's vertices from LDS. The nodes visited, tests made and
 // leaves reached are kd_walk's; only which lanes make them changes (a triangle's leaves reach its output
 // segment in another order, which the stable sort by leaf key makes irrelevant, as in the split descent).
-#ifndef BM_KD_SHARE
-#define BM_KD_SHARE 1
-#endif
 constexpr int KD_SHARE = 64;  // walks per one-wave workgroup (32 lane pairs, or 64 single lanes)
 struct KdShare {
     float tv[KD_SHARE][9];
@@ -951,7 +830,7 @@ __global__ __launch_bounds__(TB) void k_kd_top(const MeshDesc* __restrict__ mesh
     uint32_t wg = g, wpath = 0, i = 0, nq = 0;
     int wdepth = 0;
     uint32_t* const mark = (!EMIT && a.topmap) ? s_top : nullptr;
-    if constexpr (TB == 64 && BM_KD_SHARE) {  // round 0 with shared work: every lane of the wave takes part
+    if constexpr (TB == 64) {  // round 0 with shared work: every lane of the wave takes part
         float tv[9];
         if (walk) load_tri(meshes, nm, g, tv);
         if (lead) {
@@ -1011,22 +890,9 @@ __global__ __launch_bounds__(TB) void k_kd_top(const MeshDesc* __restrict__ mesh
 }
 
 // Emit pass when the count pass queued every node at depth `split` (no overflow): triangles with at most
-// KD_LEAF_CACHE leaves copy them from the cache; k_kd_sub<true> then re-walks only the queued subtrees of
-// the others — no second walk from the root. By default its work runs as extra workgroups of k_kd_sub<true>'s
-// launch (BM_KD_FUSE_COPY; the fill counters k_kd_sub<true> bumps are then zeroed by the count pass).
-__global__ __launch_bounds__(BLOCK) void k_kd_copy(KdSplitArgs a) {
-    BDIAG(12);
-    const uint32_t g = blockIdx.x * BLOCK + threadIdx.x;
-    if (g >= a.n) return;
-    a.fill[g] = 0u;
-    const uint32_t cnt = a.counts[g];
-    if (cnt > KD_LEAF_CACHE) return;
-    const uint32_t o = a.offsets[g];
-    for (uint32_t i = 0; i < cnt; ++i) {
-        a.keys[o + i] = a.cache[(size_t)i * a.n + g];
-        a.vals[o + i] = g;
-    }
-}
+// KD_LEAF_CACHE leaves copy them from the cache, as extra workgroups of k_kd_sub<true>'s launch (copy_first;
+// the fill counters k_kd_sub<true> bumps were zeroed by the count pass); its walk workgroups then re-walk
+// only the queued subtrees of the others — no second walk from the root.
 
 // Phase B: one queued node per lane (pair) — grid-stride over the queue's length, read on the device.
 // At least 4 waves per SIMD: the walk sits just above 128 VGPRs without the SLP vectorizer (build.py),
@@ -1038,7 +904,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4))) void k_
     __shared__ uint32_t stk[KD_WALK_STACK * (TB / W)];
     if (EMIT)  // the next kernel's metadata, in place of a fill launch (nothing here reads it)
         for (uint32_t z = blockIdx.x * TB + threadIdx.x; z < a.zero_words; z += gridDim.x * TB) a.zero_ptr[z] = 0u;
-    if (EMIT && a.copy_first && blockIdx.x >= a.copy_first) {  // k_kd_copy's work, in the same launch
+    if (EMIT && a.copy_first && blockIdx.x >= a.copy_first) {  // the cached leaves' copy (see above)
         const uint32_t g = (blockIdx.x - a.copy_first) * TB + threadIdx.x;
         if (g >= a.n) return;
         const uint32_t cnt = a.counts[g];
@@ -1052,7 +918,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4))) void k_
     }
     const uint32_t q = *a.qcount < a.cap ? *a.qcount : a.cap;
     const uint32_t stride = (a.copy_first ? a.copy_first : gridDim.x) * (TB / W);
-    if constexpr (TB == 64 && BM_KD_SHARE) {  // rounds of one item per pair, the round's walks sharing work
+    if constexpr (TB == 64) {  // rounds of one item per pair, the round's walks sharing work
         __shared__ KdShare S;
         const bool lead = kd_lead<PAIR>();
         for (uint32_t i = (blockIdx.x * TB + threadIdx.x) / W;;) {
@@ -1084,7 +950,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4))) void k_
         bool walk = false;
         for (; i < q; i += stride) {
             it = a.queue[i];
-            if (EMIT && a.counts[it.x] <= KD_LEAF_CACHE) continue;  // copied from the cache (k_kd_copy / k_kd_top)
+            if (EMIT && a.counts[it.x] <= KD_LEAF_CACHE) continue;  // copied from the cache
             walk = true;
             i += stride;
             break;
@@ -1684,33 +1550,16 @@ __device__ __forceinline__ vec3f kd_ray_dir(const TraceParams& p, uint32_t x, ui
 // times, and with one leaf per lane a wave ran a leaf round per lane-leaf, every other lane idle through
 // each walk in between (C2's heaviest wave: 702 loop iterations where its longest lane needs 213; the
 // oracle model in tools/kd_iters.py). K = 1 is the plain form: counting traces, whose counters are the
-// reference's work. A round tests each lane's first recorded leaf only (BM_KD_ROUND_FIRST): testing all
+// reference's work. A round tests each lane's first recorded leaf only: testing all
 // of them spent face tests on leaves behind the first hit (filled view 1.67 -> 1.59 ms, C5 1.02 ->
 // 0.95 ms); with that, K = 4 (C2 0.293 -> 0.272 ms) was where more recorded leaves stopped paying. With the
 // rounds' LDS chains gone (ballot owners, DPP prefix) K = 6 is a little better again (C2 0.211 -> 0.207 ms,
 // C5 0.637 -> 0.617; K = 8 between).
-#ifndef BM_KD_SPEC
-#define BM_KD_SPEC 6
-#endif
-#ifndef BM_KD_CB
-#define BM_KD_CB 1  // 0: child-box steps compiled out (A/B builds)
-#endif
-#ifndef BM_KD_STEPS
-#define BM_KD_STEPS 4  // child-box visits per loop iteration for a lane that keeps descending (1/2/3/4/8: C2 0.237/0.217/0.212/0.210/0.220 ms)
-#endif
-#ifndef BM_KD_DPP_SCAN
-#define BM_KD_DPP_SCAN 1  // leaf rounds: the face-count prefix by DPP row shifts and broadcasts (0: shuffles)
-#endif
-#ifndef BM_KD_OWNER_BALLOT
-#define BM_KD_OWNER_BALLOT 1  // leaf rounds: face-slot owners by window ballots (0: binary search per slot)
-#endif
-#ifndef BM_KD_ROUND_FIRST
-#define BM_KD_ROUND_FIRST 1  // a leaf round tests each lane's first recorded leaf only (0: all of them)
-#endif
-#ifndef BM_KD_XCD
-#define BM_KD_XCD 4  // tile columns per XCD run (k_kd_march_coop; 0: screen order)
-#endif
-constexpr int KD_SPEC = BM_KD_SPEC;
+constexpr int KD_SPEC = 6;
+// child-box visits per loop iteration for a lane that keeps descending (1/2/3/4/8: C2 0.237/0.217/0.212/0.210/0.220 ms)
+constexpr int KD_STEPS = 4;
+// tile columns per XCD run (k_kd_march_coop); measured against screen order
+constexpr uint32_t KD_XCD = 4;
 static_assert(KD_SPEC >= 1 && KD_SPEC <= 8, "recorded leaves per lane");
 
 template <bool COUNT, int K, bool CB>
@@ -1783,10 +1632,10 @@ __device__ __forceinline__ void kd_coop_wave(const TraceParams& p, const KdView&
                         }
                     }
                 }
-                // (BM_KD_STEPS) a lane that descends into an internal child visits it in the same
-                // iteration: one loop pass (ballot, state checks, pop test) per BM_KD_STEPS levels
+                // a lane that descends into an internal child visits it in the same iteration: one
+                // loop pass (ballot, state checks, pop test) per KD_STEPS levels
 #pragma unroll 1
-                for (int step = 0; step < BM_KD_STEPS && !need_pop; ++step) {
+                for (int step = 0; step < KD_STEPS && !need_pop; ++step) {
                     if (COUNT) ++c_nodes;
                     const uint4* cp = kv.cnodes + 4 * (size_t)ref;
                     const uint4 c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
@@ -1858,7 +1707,6 @@ __device__ __forceinline__ void kd_coop_wave(const TraceParams& p, const KdView&
         // ---- the recorded leaves, tested by the whole wave ------------------------------------------
         ++rounds;
         const uint64_t round_t0 = COUNT ? __builtin_amdgcn_s_memrealtime() : 0;  // (diagnostic traces)
-#if BM_KD_ROUND_FIRST
         // each lane's first recorded leaf only: no face is tested past the leaf the reference stops at;
         // a lane whose first leaf has no hit moves its next recorded leaf up for the next round (which
         // runs at once when no lane has to walk)
@@ -1874,24 +1722,14 @@ __device__ __forceinline__ void kd_coop_wave(const TraceParams& p, const KdView&
             }
         }
         if (COUNT) c_faces += ccnt;
-#if BM_KD_DPP_SCAN
+        // the face-count prefix by DPP row shifts and broadcasts (wave_incl_add)
         const uint32_t incl = wave_incl_add(ccnt);
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-#else
-        uint32_t incl = ccnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = __shfl_up(incl, o);
-            if (lane >= o) incl += v;
-        }
-        const uint32_t total = __shfl(incl, 63);
-#endif
-#if BM_KD_OWNER_BALLOT
         // Owners by window: for the 64 face slots [base, base + 64), each lane with faces whose first
         // slot lies in the window marks that position with its lane id (own[], in sincl's place), a
         // ballot of the marked positions gives each slot the nearest mark at or below it, and a slot
         // before the window's first mark belongs to the previous window's last owner — two LDS round
-        // trips and a ballot where the binary search took six dependent reads.
+        // trips and a ballot where a binary search per slot took six dependent reads.
         L.sbest[lane] = ~0ull;
         const uint32_t excl = incl - ccnt;
         uint32_t carry = 0;
@@ -1910,23 +1748,6 @@ __device__ __forceinline__ void kd_coop_wave(const TraceParams& p, const KdView&
             const uint32_t f = j - (uint32_t)__shfl((int)excl, (int)lo);
             const uint32_t start = (uint32_t)__shfl((int)cstart, (int)lo);
             __builtin_amdgcn_wave_barrier();
-#else
-        L.sincl[lane] = incl;
-        L.sbest[lane] = ~0ull;
-        __syncthreads();
-        for (uint32_t j = lane; j < ((total + 63) & ~63u); j += 64) {
-            // owner: the lowest lane whose inclusive sum exceeds j (lanes with no faces never are); every
-            // lane takes part in the shuffle (lanes past the total with the last face's owner)
-            const uint32_t jj = min(j, total - 1u);
-            uint32_t lo = 0, hi = 63;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (L.sincl[mid] > jj) hi = mid;
-                else lo = mid + 1;
-            }
-            const uint32_t f = jj - (lo ? L.sincl[lo - 1] : 0u);
-            const uint32_t start = (uint32_t)__shfl((int)cstart, (int)lo);
-#endif
             if (j < total) {
                 const float4* ft = kv.ftris + 3 * ((size_t)start + f);
                 const float4 od = L.sdir[lo];
@@ -1963,98 +1784,6 @@ __device__ __forceinline__ void kd_coop_wave(const TraceParams& p, const KdView&
                 state = np ? (walked ? KD_PENDING : KD_TRAVERSE) : (walked ? KD_DONE : KD_TRAVERSE);
             }
         }
-#else
-        if (CB && cbl && np) {  // leaf indices -> first face record and face counts (loads issued together)
-            const uint32_t* lw = reinterpret_cast<const uint32_t*>(kv.leaves);
-            uint32_t acc = 0;
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-                if (k < (int)np) {
-                    const uint32_t li = pst[k];
-                    pst[k] = lw[8 * (size_t)li + 3];
-                    acc += lw[8 * (size_t)li + 7];
-                    pin[k] = acc;
-                }
-        }
-        uint32_t cnt = 0;
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            if (k + 1 == (int)np) cnt = pin[k];
-        if (COUNT) c_faces += cnt;
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = __shfl_up(incl, o);
-            if (lane >= o) incl += v;
-        }
-        const uint32_t total = __shfl(incl, 63);
-        L.sincl[lane] = incl;
-        L.sbest[lane] = ~0ull;
-        __syncthreads();
-        for (uint32_t j = lane; j < ((total + 63) & ~63u); j += 64) {
-            // owner: the lowest lane whose inclusive sum exceeds j (lanes with no faces never are); every
-            // lane takes part in the shuffles below (lanes past the total with the last face's owner)
-            const uint32_t jj = min(j, total - 1u);
-            uint32_t lo = 0, hi = 63;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (L.sincl[mid] > jj) hi = mid;
-                else lo = mid + 1;
-            }
-            const uint32_t local = jj - (lo ? L.sincl[lo - 1] : 0u);
-            // which of the owner's recorded leaves: the first whose inclusive count exceeds `local`
-            uint32_t q = 0, base = 0, start = 0, prev = 0;
-            bool found = false;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const uint32_t pk = (uint32_t)__shfl((int)pin[k], (int)lo);
-                const uint32_t sk = (uint32_t)__shfl((int)pst[k], (int)lo);
-                if (!found && local < pk) {
-                    found = true;
-                    q = (uint32_t)k;
-                    base = prev;
-                    start = sk;
-                }
-                prev = pk;
-            }
-            if (j < total) {
-                const uint32_t f = local - base;
-                const float4* ft = kv.ftris + 3 * ((size_t)start + f);
-                const float4 od = L.sdir[lo];
-                float t, u, v;
-                if (tri_test(ft[0], ft[1], ft[2], eye, v3(od.x, od.y, od.z), t, u, v) && t < FLT_MAXF) {
-                    // the first recorded leaf with a hit, then the smallest t, then the earliest face
-                    // (-0 -> +0: equal t, earliest face)
-                    const uint32_t tb = __float_as_uint(t + 0.0f);
-                    const uint32_t ot = (tb & 0x80000000u) ? ~tb : (tb | 0x80000000u);
-                    atomicMin(&L.sbest[lo], ((unsigned long long)q << 40) | ((unsigned long long)ot << 8) | f);
-                }
-            }
-        }
-        __syncthreads();
-        if (np) {
-            const unsigned long long best = L.sbest[lane];
-            if (best != ~0ull) {  // the first leaf with a hit ends the march (:427-431)
-                const uint32_t q = (uint32_t)(best >> 40), f = (uint32_t)best & 0xFFu;
-                uint32_t start = 0;
-#pragma unroll
-                for (int k = 0; k < K; ++k)
-                    if (k == (int)q) start = pst[k];
-                const float4* ft = kv.ftris + 3 * ((size_t)start + f);
-                const float4 a = ft[0];
-                float t, u, v;
-                tri_test(a, ft[1], ft[2], eye, dir, t, u, v);
-                dclosest = t;
-                fclosest = __float_as_uint(a.w);
-                tu = u;
-                tvv = v;
-                state = KD_DONE;
-            } else {
-                state = walked ? KD_DONE : KD_TRAVERSE;
-            }
-            np = 0;
-        }
-#endif
         __syncthreads();  // sincl/sbest are rewritten by the next round
         if (COUNT) round_ticks += __builtin_amdgcn_s_memrealtime() - round_t0;
     }
@@ -2093,8 +1822,8 @@ __global__ __launch_bounds__(64) void k_kd_march_coop(const TraceParams p, const
     // tile columns share an XCD and its L2 (the kd records their rays walk); measured 1-2 % on C2, C5 and
     // the filled view (G = 4 against screen order, tools/ref_time.py).
     uint32_t bx = blockIdx.x;
-    if (BM_KD_XCD > 0 && (gridDim.x & 7u) == 0) {
-        constexpr uint32_t G = BM_KD_XCD > 0 ? BM_KD_XCD : 1, SPAN = 8 * G;
+    if ((gridDim.x & 7u) == 0) {
+        constexpr uint32_t G = KD_XCD, SPAN = 8 * G;
         if (bx < gridDim.x / SPAN * SPAN) {
             const uint32_t q = bx >> 3;
             bx = G * (8 * (q / G) + (bx & 7u)) + q % G;
@@ -2107,7 +1836,7 @@ __global__ __launch_bounds__(64) void k_kd_march_coop(const TraceParams p, const
     uint32_t iters = 0, rounds = 0;
     uint64_t round_ticks = 0;
     constexpr int K = COUNT && !DIAG ? 1 : KD_SPEC;  // counting traces: the reference's work
-    constexpr bool CB = (!COUNT || DIAG) && BM_KD_CB;
+    constexpr bool CB = !COUNT || DIAG;
     kd_coop_wave<COUNT, K, CB>(p, kv, L, x, y, inside, c_nodes, c_faces, hit, iters, rounds,
                                                                      round_ticks);
     if (COUNT && !DIAG) {  // (a diagnostic trace reports per-wave work; 3 same-address atomics per wave
@@ -2433,52 +2162,45 @@ static KdSplitArgs split_args(const KdBuild& k) {
 }
 
 template <bool EMIT, bool PAIR, int TB, bool GRID>
-static void launch_kd_split_grid(const KdBuild& k, const KdSplitArgs& a, bool top, bool fuse_copy, hipStream_t s) {
+static void launch_kd_split_grid(const KdBuild& k, const KdSplitArgs& a, bool top, hipStream_t s) {
     constexpr uint32_t W = kd_w<PAIR>();
     if (top) k_kd_top<EMIT, PAIR, TB, GRID><<<blocks_for(W * k.n, TB), TB, 0, s>>>(k.meshes, k.num_meshes, a);
     // the same lanes in flight as 1024 workgroups of 256
     const uint32_t sub_blocks = std::min<uint32_t>(blocks_for(W * k.queue_cap, TB), 1024u * (256 / TB));
     KdSplitArgs b = a;
     uint32_t grid = sub_blocks;
-    if (EMIT && fuse_copy) {  // k_kd_copy's triangles as extra workgroups after the walks'
+    if (!top) {  // the cached leaves' copy as extra workgroups after the walks'
         b.copy_first = sub_blocks;
         grid += blocks_for(k.n, TB);
     }
     k_kd_sub<EMIT, PAIR, TB, GRID><<<grid, TB, 0, s>>>(k.meshes, k.num_meshes, b);
 }
 template <bool EMIT, bool PAIR, int TB>
-static void launch_kd_split_tb(const KdBuild& k, const KdSplitArgs& a, bool top, bool fuse_copy, hipStream_t s) {
-    if (a.grid_exact) launch_kd_split_grid<EMIT, PAIR, TB, true>(k, a, top, fuse_copy, s);
-    else launch_kd_split_grid<EMIT, PAIR, TB, false>(k, a, top, fuse_copy, s);
+static void launch_kd_split_tb(const KdBuild& k, const KdSplitArgs& a, bool top, hipStream_t s) {
+    if (a.grid_exact) launch_kd_split_grid<EMIT, PAIR, TB, true>(k, a, top, s);
+    else launch_kd_split_grid<EMIT, PAIR, TB, false>(k, a, top, s);
 }
-// The emit pass's cached-leaf copy inside k_kd_sub's launch (round 6; 0 restores the separate k_kd_copy)
-#ifndef BM_KD_FUSE_COPY
-#define BM_KD_FUSE_COPY 1
-#endif
 
-// The triangles' leaf counters and (for a fused copy) fill counters are zeroed by the count pass's k_kd_top,
-// the fill counters otherwise by the emit pass's k_kd_top or k_kd_copy; the queue's count word and overflow flag by a memset (count pass, or an emit pass that walks
-// from the root again). BM_PARAM_KD_TB: lanes per workgroup of k_kd_top / k_kd_sub (64 or 256).
+// top: k_kd_top walks from the root (the count pass, or an emit pass after a queue overflow); else the emit
+// pass reuses the count pass's queue and copies the cached leaves inside k_kd_sub's launch.
+// The triangles' leaf counters and (for an emit pass that reuses the queue) fill counters are zeroed by the
+// count pass's k_kd_top, the fill counters otherwise by the emit pass's k_kd_top; the queue's count word and
+// overflow flag by a memset (count pass, or an emit pass that walks from the root again). BM_PARAM_KD_TB: lanes per workgroup of k_kd_top / k_kd_sub (64 or 256).
 template <bool EMIT>
 static hipError_t launch_kd_split(const KdBuild& k, hipStream_t s) {
     hipError_t e;
     const KdSplitArgs a = split_args(k);
-    const bool fuse_copy = EMIT && k.reuse_queue && BM_KD_FUSE_COPY;  // fill counters: zeroed by the count pass
-    if (EMIT && k.reuse_queue) {  // the count pass's queue holds every subtree: no walk from the root
-        if (!fuse_copy) k_kd_copy<<<blocks_for(k.n, BLOCK), BLOCK, 0, s>>>(a);
-        BM_LAUNCH_CHECK();
-    } else if (!(!EMIT && k.qcount_zeroed) && (e = hipMemsetAsync(k.qcount, 0, 8, s)) != hipSuccess) {
+    const bool top = !(EMIT && k.reuse_queue);  // else the count pass's queue holds every subtree
+    if (top && !(!EMIT && k.qcount_zeroed) && (e = hipMemsetAsync(k.qcount, 0, 8, s)) != hipSuccess)
         return e;  // count word + overflow flag (the count pass: zeroed by launch_gather already)
-    }
     const bool pair = !k.tune || k.tune->get(BM_PARAM_KD_PAIR, 1) != 0;
     const int tb = k.tune ? (int)k.tune->get(BM_PARAM_KD_TB, 64) : 64;
-    const bool top = !(EMIT && k.reuse_queue);
     if (tb == 256) {
-        if (pair) launch_kd_split_tb<EMIT, true, 256>(k, a, top, fuse_copy, s);
-        else launch_kd_split_tb<EMIT, false, 256>(k, a, top, fuse_copy, s);
+        if (pair) launch_kd_split_tb<EMIT, true, 256>(k, a, top, s);
+        else launch_kd_split_tb<EMIT, false, 256>(k, a, top, s);
     } else {
-        if (pair) launch_kd_split_tb<EMIT, true, 64>(k, a, top, fuse_copy, s);
-        else launch_kd_split_tb<EMIT, false, 64>(k, a, top, fuse_copy, s);
+        if (pair) launch_kd_split_tb<EMIT, true, 64>(k, a, top, s);
+        else launch_kd_split_tb<EMIT, false, 64>(k, a, top, s);
     }
     BM_LAUNCH_CHECK();
     return hipSuccess;

@@ -49,8 +49,8 @@ def compare(rec, tris, keys, perm, orc):
 
 
 @pytest.mark.parametrize("n,dup", [(2, 0), (511, 0), (512, 0), (513, 0), (1024, 300), (1025, 0), (4097, 2000),
-                                   (16384, 0), (70000, 0), (140000, 5000), (300000, 3000), (524289, 0),
-                                   (600000, 20000)])
+                                   (16384, 0), (70000, 0), (131072, 0), (131073, 0), (140000, 5000),
+                                   (300000, 3000), (524289, 0), (600000, 20000)])
 @pytest.mark.parametrize("width", [4, 2])
 def test_build_and_refit_at_regime_edges(oracle, n, dup, width):
     meshes = soup(n, seed=n + width, dup=dup)
