@@ -1377,6 +1377,9 @@ static inline uint32_t order_key8(float tn, uint32_t slot) {
  * distance (ties: lower slot first). Returns the next ref, or EMPTY_REF when no child is hit. */
 /* per thread: the bench's CPU baseline calls orc_bvh_trace from several threads at once */
 static _Thread_local int g_max_stack;
+/* Optional per-ray depth record (orc_set_ray_depth): g_ray_sp is the deepest sp of the ray being traced. */
+static _Thread_local uint32_t* g_ray_depth = NULL;
+static _Thread_local int g_ray_sp;
 static uint32_t visit_node(const orc_bvh* b, uint32_t node, const float* o, const float* inv, float tmax,
                            uint32_t* stk_ref, float* stk_t, int* sp) {
     const int W = (int)b->width;
@@ -1409,6 +1412,7 @@ static uint32_t visit_node(const orc_bvh* b, uint32_t node, const float* o, cons
         (*sp)++;
     }
     if (*sp > g_max_stack) g_max_stack = *sp;
+    if (*sp > g_ray_sp) g_ray_sp = *sp;
     return by_ref[0];
 }
 
@@ -1417,6 +1421,7 @@ static uint32_t visit_node(const orc_bvh* b, uint32_t node, const float* o, cons
 static uint32_t* g_ray_stats = NULL;
 void orc_set_ray_stats(uint32_t* per_ray) { g_ray_stats = per_ray; g_max_stack = 0; }
 int32_t orc_max_stack(void) { return g_max_stack; }
+void orc_set_ray_depth(uint32_t* per_ray) { g_ray_depth = per_ray; }
 
 int32_t orc_bvh_trace(const orc_bvh* b, const float* rays, uint32_t begin, uint32_t end,
                       const float eye[3], const float orient[9], uint32_t* packed,
@@ -1434,6 +1439,7 @@ int32_t orc_bvh_trace(const orc_bvh* b, const float* rays, uint32_t begin, uint3
         float stk_t[TRACE_STACK];
         int sp = 0;
         uint32_t next = 0; /* root record */
+        g_ray_sp = 0;
         for (;;) {
             if (next == EMPTY_REF) {
                 /* pop until an entry that can still hold a closer hit */
@@ -1465,6 +1471,7 @@ int32_t orc_bvh_trace(const orc_bvh* b, const float* rays, uint32_t begin, uint3
             c_nodes++;
             next = visit_node(b, next, eye, inv, tbest, stk_ref, stk_t, &sp);
         }
+        if (g_ray_depth) g_ray_depth[i] = (uint32_t)g_ray_sp;
         if (g_ray_stats) {
             g_ray_stats[2 * (size_t)i] = (uint32_t)(c_nodes - n0);
             g_ray_stats[2 * (size_t)i + 1] = (uint32_t)(c_tris - t0);
@@ -1511,6 +1518,7 @@ int32_t orc_bvh_shadow(const orc_bvh* b, const float* rays, uint32_t begin, uint
     for (uint32_t i = begin; i < end; ++i) {
         if (tri_id[i] == NO_TRI) {
             shadow[i] = 0;
+            if (g_ray_depth) g_ray_depth[i] = 0;
             continue;
         }
         float dir[3], o[3], d[3], inv[3];
@@ -1521,6 +1529,7 @@ int32_t orc_bvh_shadow(const orc_bvh* b, const float* rays, uint32_t begin, uint
         float stk_t[TRACE_STACK];
         int sp = 0, occ = 0;
         uint32_t next = 0;
+        g_ray_sp = 0;
         for (;;) {
             if (next == EMPTY_REF) {
                 if (sp == 0) break;
@@ -1545,6 +1554,7 @@ int32_t orc_bvh_shadow(const orc_bvh* b, const float* rays, uint32_t begin, uint
             next = visit_node(b, next, o, inv, 1.0f, stk, stk_t, &sp);
         }
         shadow[i] = (uint8_t)occ;
+        if (g_ray_depth) g_ray_depth[i] = (uint32_t)g_ray_sp;
         c_occ += (uint64_t)occ;
     }
     if (counters) {

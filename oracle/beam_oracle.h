@@ -129,6 +129,12 @@ int32_t  orc_bvh_trace(const orc_bvh* b, const float* rays, uint32_t begin, uint
 void     orc_set_ray_stats(uint32_t* per_ray);
 /* Deepest traversal stack seen since the last orc_set_ray_stats call. */
 int32_t  orc_max_stack(void);
+/* Record each ray's deepest traversal stack (1 u32 per pixel index: the largest number of entries its
+ * stack held after a node step's pushes) in later orc_bvh_trace and orc_bvh_shadow calls of the calling
+ * thread; NULL turns it off. orc_bvh_shadow records the shadow ray's own depth, 0 where none is cast.
+ * The GPU kernels push in the same order (the traversal counters match), so this is the depth their
+ * stacks must reach: entries past a kernel's LDS depth live in its global overflow area. */
+void     orc_set_ray_depth(uint32_t* per_ray);
 
 /* One shadow ray per primary hit (build-defined, the reference has none):
  * origin = eye + dir * (t * 0.9999f), direction = light - origin (unnormalised); the pixel is

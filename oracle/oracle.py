@@ -86,6 +86,8 @@ def load_oracle() -> C.CDLL:
         lib.orc_bvh_export.argtypes = [C.c_void_p, u32p, u32p, u32p, u32p]
         lib.orc_bvh_trace.argtypes = [C.c_void_p, f32p, C.c_uint32, C.c_uint32, f32p, f32p, u32p, u32p, f32p, u64p]
         lib.orc_bvh_trace.restype = C.c_int32
+        lib.orc_set_ray_depth.argtypes = [u32p]
+        lib.orc_set_ray_depth.restype = None
         lib.orc_brute_trace.argtypes = [mp, C.c_uint32, f32p, C.c_uint32, C.c_uint32, f32p, f32p, u32p, u32p, f32p]
         lib.orc_brute_trace.restype = C.c_int32
         u8p = C.POINTER(C.c_uint8)
@@ -353,7 +355,16 @@ class OrcBVH:
                                 _p(perm, C.c_uint32))
         return rec, tris[: self.n], keys[: self.n], perm[: self.n]
 
-    def render(self, rays, eye, orient, begin=0, end=None, counters=False):
+    def _depth_hook(self, depth, n):
+        """Validate a caller's per-ray depth array and switch orc_set_ray_depth on for this thread."""
+        if depth is None:
+            return
+        if depth.dtype != np.uint32 or depth.shape != (n,) or not depth.flags.c_contiguous:
+            raise ValueError(f"depth must be a contiguous uint32 array of shape ({n},)")
+        self.lib.orc_set_ray_depth(_p(depth, C.c_uint32))
+
+    def render(self, rays, eye, orient, begin=0, end=None, counters=False, depth=None):
+        """depth: optional uint32[n]; entries [begin, end) receive each ray's deepest traversal stack."""
         n = rays.shape[0]
         end = n if end is None else end
         packed, tri, t = Oracle._frame(n)
@@ -361,23 +372,34 @@ class OrcBVH:
         eye = np.asarray(eye, np.float32)
         orient = np.asarray(orient, np.float32).reshape(9)
         rays = np.ascontiguousarray(rays, np.float32)
-        err = self.lib.orc_bvh_trace(self.h, _p(rays, C.c_float), begin, end, _p(eye, C.c_float),
-                                     _p(orient, C.c_float), _p(packed, C.c_uint32), _p(tri, C.c_uint32),
-                                     _p(t, C.c_float), _p(cnt, C.c_uint64))
+        self._depth_hook(depth, n)
+        try:
+            err = self.lib.orc_bvh_trace(self.h, _p(rays, C.c_float), begin, end, _p(eye, C.c_float),
+                                         _p(orient, C.c_float), _p(packed, C.c_uint32), _p(tri, C.c_uint32),
+                                         _p(t, C.c_float), _p(cnt, C.c_uint64))
+        finally:
+            if depth is not None:
+                self.lib.orc_set_ray_depth(None)
         if err:
             raise RuntimeError(f"orc_bvh_trace error {err}")
         res = (packed[begin:end], tri[begin:end], t[begin:end])
         return (res + (cnt,)) if counters else res
 
-    def shadow(self, rays, eye, orient, light, tri, t, counters=False):
-        """One any-hit shadow ray per primary hit (orc_bvh_shadow); returns u8 per pixel."""
+    def shadow(self, rays, eye, orient, light, tri, t, counters=False, depth=None):
+        """One any-hit shadow ray per primary hit (orc_bvh_shadow); returns u8 per pixel.
+        depth: optional uint32[n] for each shadow ray's deepest traversal stack (0 where none is cast)."""
         n = rays.shape[0]
         out = np.zeros(n, np.uint8)
         cnt = np.zeros(3, np.uint64)
         a = _shadow_args(rays, eye, orient, light, tri, t)
-        err = self.lib.orc_bvh_shadow(self.h, _p(a[0], C.c_float), 0, n, _p(a[1], C.c_float), _p(a[2], C.c_float),
-                                      _p(a[3], C.c_float), _p(a[4], C.c_uint32), _p(a[5], C.c_float),
-                                      _p(out, C.c_uint8), _p(cnt, C.c_uint64))
+        self._depth_hook(depth, n)
+        try:
+            err = self.lib.orc_bvh_shadow(self.h, _p(a[0], C.c_float), 0, n, _p(a[1], C.c_float),
+                                          _p(a[2], C.c_float), _p(a[3], C.c_float), _p(a[4], C.c_uint32),
+                                          _p(a[5], C.c_float), _p(out, C.c_uint8), _p(cnt, C.c_uint64))
+        finally:
+            if depth is not None:
+                self.lib.orc_set_ray_depth(None)
         if err:
             raise RuntimeError(f"orc_bvh_shadow error {err}")
         return (out, cnt) if counters else out
