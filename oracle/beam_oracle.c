@@ -1458,7 +1458,7 @@ int32_t orc_bvh_trace(const orc_bvh* b, const float* rays, uint32_t begin, uint3
                     float u = 0, v = 0;
                     float t = tri_intersect_e(eye, dir, v0, e1, e2, &u, &v);
                     c_tris++;
-                    if (t > 0.0f && t != FLT_MAX && (t < tbest || (t == tbest && r[3] < ibest))) {
+                    if (t > 0.0f && t < FLT_MAX && (t < tbest || (t == tbest && r[3] < ibest))) {
                         tbest = t;
                         ibest = r[3];
                         bu = u;

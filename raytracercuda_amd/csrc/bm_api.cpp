@@ -173,6 +173,7 @@ struct bm_scene {
     bool replicas_clean = false;       // bounds' gather replicas left zero by the last LBVH build/refit (bm_build.hip)
     uint32_t* hbounds = nullptr;       // pinned: the last build's scene box (ordered images, 6 words)
     hipEvent_t hbounds_ev = nullptr;   // ... valid once this has completed; word 8: the build's sort skew word
+    bool hbounds_seen = false;         // a trace has found hbounds_ev complete since the last build or refit
     hipEvent_t staging_done = nullptr, ev0 = nullptr, ev1 = nullptr;
     uint32_t sort_path = 0;            // BM_SORT_* of the last build (MSD until its skew word is read)
     bool orig_valid = false;           // tri_orig holds the last build's original-order records (reshade)
@@ -1328,6 +1329,7 @@ static int32_t scene_build_impl(bm_scene* s, bm_build_stats* stats, bool refit) 
             BM_HIP(ctx, hipMemcpyAsync(s->hbounds + 8, b.bounds + bm::build_sort_skew_word(), sizeof(uint32_t),
                                        hipMemcpyDeviceToHost, ctx->stream));
         BM_HIP(ctx, hipEventRecord(s->hbounds_ev, ctx->stream));
+        s->hbounds_seen = false;
     }
     s->kd = ctx->reference_kd;
     s->hash = ctx->reference_hash;
@@ -1347,9 +1349,10 @@ static int32_t scene_build_impl(bm_scene* s, bm_build_stats* stats, bool refit) 
     if (ctx->reference_kd) s->sort_path = !n ? 0u : s->kd_top_rank ? BM_SORT_KD_RANKED : BM_SORT_LSD;  // the pair sort
     if (stats) {
         BM_HIP(ctx, hipEventSynchronize(s->ev1));
-        if (s->sort_path == BM_SORT_MSD) {
+        if (!ctx->reference_kd && !ctx->reference_hash) {  // a call that waits for its statistics has the box too
             BM_HIP(ctx, hipEventSynchronize(s->hbounds_ev));
-            if (s->hbounds[8]) s->sort_path = BM_SORT_MSD_SKEW;
+            s->hbounds_seen = true;
+            if (s->sort_path == BM_SORT_MSD && s->hbounds[8]) s->sort_path = BM_SORT_MSD_SKEW;
         }
         stats->sort_path = s->sort_path;
         stats->fused_front = front ? 1u : 0u;
@@ -1640,6 +1643,25 @@ static double scene_coverage(const bm_camera* c, const bm_scene* s, const float*
     return w * h / (W * H);
 }
 
+// Whether the eye lies within the distance of the scene over which the box prune is conservative: within
+// BM_ENVELOPE_EXTENTS times the largest side of the scene's box of that box's centre, which is how that
+// distance was measured. Wave packets run only there: they visit subtrees in their first
+// lane's order, and a ray's closest hit is independent of the visit order only while no box that holds it can
+// fail tn <= tbest by rounding. Beyond, the quad kernel keeps each ray's own order, which is the oracle's.
+// The bounds are the last build's host copy; the caller has seen hbounds_ev complete.
+static bool eye_in_envelope(const bm_scene* s, const float* eye3) {
+    double d2 = 0, side = 0;
+    for (int a = 0; a < 3; ++a) {
+        const double lo = bm::bounds_lo(s->hbounds[a]), hi = bm::bounds_hi(s->hbounds[3 + a]);
+        if (!(lo <= hi)) return true;  // an empty scene: nothing to visit
+        const double d = eye3[a] - 0.5 * (lo + hi);
+        d2 += d * d;
+        side = std::max(side, hi - lo);
+    }
+    // inclusive of the measured distance itself: an eye placed at it in float32 may lie an ulp beyond
+    return d2 <= (double)BM_ENVELOPE_EXTENTS * BM_ENVELOPE_EXTENTS * side * side * (1.0 + 0x1p-16);
+}
+
 // The traversal-stack overflow area of a persistent launch of p.variant over p.bvh_width records: sized
 // for the largest persistent grid (persistent_blocks x 256 slots; a quad kernel's slot is blockIdx.x *
 // QRAYS + ray), grow-only. rt: the render target traced into (null: a ray query, on the context stream).
@@ -1794,7 +1816,15 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
     p.prio_level = ctx->prio_level;
     p.refill_min = ctx->refill_min;
     p.sched = ctx->sched >= 0 ? (uint32_t)ctx->sched : rt->stream ? 1u : 2u;
-    const bool packet = p.variant == bm::TRACE_PACKET && !rq.count && !rq.light && s->width == 4;
+    bool packet = p.variant == bm::TRACE_PACKET && !rq.count && !rq.light && s->width == 4;
+    // packets within the envelope only; a far eye takes the quad kernel (the profile entry keeps what it asked
+    // for). The scene's box is the last build's host copy: while that copy is still on its way, right after a
+    // build or refit, the trace takes quads too and nothing waits, as scene_coverage does not
+    if (packet && !rq.diag && s->hbounds && s->n) {
+        if (!s->hbounds_seen) s->hbounds_seen = hipEventQuery(s->hbounds_ev) == hipSuccess;
+        packet = s->hbounds_seen && eye_in_envelope(s, eye3);
+        if (!packet) p.variant = bm::TRACE_QUAD;
+    }
     if (packet) p.persistent_blocks = ctx->persistent_blocks;  // the packet kernel's persistent grid (no overflow area)
     if (p.sched == 2 && (p.variant == bm::TRACE_QUAD || packet)) {  // (quad tiles outnumber 8x8 packet tiles)
         const size_t ntiles = bm::quad_tiles(p.width, p.local_rows);

@@ -102,7 +102,7 @@ __device__ __forceinline__ void pair_closest(const TraceParams& p, const PS& st,
                 if (k0 + h < cnt) {
                     const float4 a = p.tris[3 * k + 0], b = p.tris[3 * k + 1], cc = p.tris[3 * k + 2];
                     float tt, uu, vv;
-                    if (tri_test(a, b, cc, eye, dir, tt, uu, vv) && tt > 0.0f && tt != 3.40282347e+38f) {
+                    if (tri_test(a, b, cc, eye, dir, tt, uu, vv) && tt > 0.0f && tt < 3.40282347e+38f) {
                         t = tt;
                         id = f2u(a.w);
                         u = uu;
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(BLOCK) BM_TRACE_OCCUPANCY void k_trace_quad_fetch(c
                 if (k0 + c < cnt) {
                     const float4 a = p.tris[3 * k + 0], b = p.tris[3 * k + 1], cc = p.tris[3 * k + 2];
                     float tt, uu, vv;
-                    if (tri_test(a, b, cc, eye, dir, tt, uu, vv) && tt > 0.0f && tt != 3.40282347e+38f) {
+                    if (tri_test(a, b, cc, eye, dir, tt, uu, vv) && tt > 0.0f && tt < 3.40282347e+38f) {
                         t = tt;
                         id = f2u(a.w);
                         u = uu;

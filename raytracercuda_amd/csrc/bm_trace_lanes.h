@@ -202,7 +202,7 @@ __device__ __forceinline__ bool trace_pixel(const TraceParams& p, STACK& st, uin
                     if (!(u < 0 || u > 1) && !(v < 0 || v + u > 1)) {
                         const float t = dot(e2, qv) * idet;
                         const uint32_t id = f2u(a.w);
-                        if (t > 0.0f && t != 3.40282347e+38f && (t < tbest || (t == tbest && id < ibest))) {
+                        if (t > 0.0f && t < 3.40282347e+38f && (t < tbest || (t == tbest && id < ibest))) {
                             tbest = t;
                             ibest = id;
                             bu = u;

@@ -17,8 +17,13 @@ namespace {
 // closest hit, so a subtree is entered only by lanes whose own traversal would enter it; every lane
 // keeps its own (t, id) closest hit with lowest-id ties, which does not depend on the order the
 // subtrees are visited in — the frame equals the oracle's (the visit order and the COUNT counters do
-// not, so counting traces keep the quad kernel). Children are ordered by the entry distances of the
-// packet's first lane (children that lane misses after).
+// not, so counting traces keep the quad kernel). That holds where the box prune is conservative: for
+// eyes within 32 scene extents of the scene. Farther out a box that holds a ray's
+// closest hit can fail tn <= tbest by rounding, whether it does depends on what was found before it,
+// and a packet visits in its first lane's order (measured at 4096 extents: on a pixel or two of a frame
+// it kept the hit brute force finds where the per-ray order loses it). So the host launches packets for
+// eyes within that distance only and the quad kernel beyond (bm_api.cpp eye_in_envelope). Children are
+// ordered by the entry distances of the packet's first lane (children that lane misses after).
 // Stack bound: the BVH4 levels of a < 64-level Karras tree are < 32, a packet step pushes <= 3
 // siblings, and the stack holds siblings of the current path only: PK_DEPTH = MAX_STACK entries.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -101,7 +106,7 @@ __device__ __forceinline__ void packet_walk(const TraceParams& p, int lane, uint
                             const float4 a = make_float4(u2f(r[j][0].x), u2f(r[j][0].y), u2f(r[j][0].z), 0.f);
                             const float4 b = make_float4(u2f(r[j][1].x), u2f(r[j][1].y), u2f(r[j][1].z), 0.f);
                             const float4 c = make_float4(u2f(r[j][2].x), u2f(r[j][2].y), u2f(r[j][2].z), 0.f);
-                            if (tri_test(a, b, c, eye, dir, tt, uu, vv) && tt > 0.0f && tt != 3.40282347e+38f) {
+                            if (tri_test(a, b, c, eye, dir, tt, uu, vv) && tt > 0.0f && tt < 3.40282347e+38f) {
                                 const uint32_t id = r[j][0].w;
                                 if (tt < tbest || (tt == tbest && id < ibest)) {
                                     tbest = tt;

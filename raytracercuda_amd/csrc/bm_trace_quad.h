@@ -214,7 +214,7 @@ __device__ __forceinline__ void quad_closest(const TraceParams& p, const QS& st,
                     // pieces was measured against this and not kept: DESIGN.md §5)
                     const float4 a = p.tris[3 * k + 0], b = p.tris[3 * k + 1], cc = p.tris[3 * k + 2];
                     float tt, uu, vv;
-                    if (tri_test(a, b, cc, eye, dir, tt, uu, vv) && tt > 0.0f && tt != 3.40282347e+38f) {
+                    if (tri_test(a, b, cc, eye, dir, tt, uu, vv) && tt > 0.0f && tt < 3.40282347e+38f) {
                         t = tt;
                         id = f2u(a.w);
                         u = uu;
