@@ -206,7 +206,7 @@ int32_t bm_context_start_comm(bm_context* ctx, int32_t rank, int32_t size, const
 #define BM_PARAM_TRACE_PRIO_AFTER 3   /* steps before a long-running wave raises its priority */
 #define BM_PARAM_TRACE_PRIO_LEVEL 4   /* that priority (0-3) */
 #define BM_PARAM_TRACE_REFILL_MIN 5   /* quad-fetch variant: idle quads that trigger a refill */
-#define BM_PARAM_CULL_TILES 6         /* compacted trace: 8x8 tiles per culling workgroup region */
+#define BM_PARAM_CULL_TILES 6         /* compacted trace: 8x8 tiles per culling workgroup region (at most 2^16) */
 #define BM_PARAM_TRACE_AUTO_COMPACT 7 /* 0: never switch sparse in-flight views to cull + compacted quads */
 #define BM_PARAM_TRACE_GRID 8         /* cap of the persistent trace grid (workgroups) */
 #define BM_PARAM_READBACK_SYNC 9      /* 1: mid-build count readbacks by copy + stream sync (A/B) */
@@ -616,6 +616,14 @@ void bm_rt_destroy(bm_rt* rt);
  * a reject — packed colour bits, normalised n.z, pad). tests/test_gpu_glm_pin.py compares them bit
  * for bit with the reference's glm 0.9.9.0 (tests/golden/glm_pin.npz). */
 int32_t bm_debug_primitives(bm_context* ctx, uint32_t n, const float* in, float* out);
+/* Test hook of the cost-ordered schedule (BM_PARAM_TRACE_SCHED 2): the table of 10-ns tick counts per 4x4
+ * quad-kernel tile that each trace of this target records and the next one sorts its tiles by. set (non-null):
+ * the table is made to hold at least n words and the n host words are copied in on the target's stream; the
+ * next trace uses them as given (no zero fill). get (non-null): n words are copied out once the stream's work
+ * has completed (after the set, when both are given; BM_ERROR_NOT_BUILT when the table holds fewer).
+ * Synchronous. BM_ERROR_INVALID_PARAMETER for a multi-device context, n == 0 or both pointers null.
+ * tests/test_gpu_tile_order.py traces injected tables against the oracle. */
+int32_t bm_rt_debug_tile_costs(bm_rt* rt, uint32_t n, const uint32_t* set, uint32_t* get);
 
 /* ---- OBJ ingest: TestProgram's Model::load (TestProgram/Model.cpp:26-126) without Assimp ------ */
 /* Host-side parse (no device work): one mesh per material run (a `usemtl` after faces, or `o`/`g`,

@@ -646,6 +646,19 @@ class IRenderTarget:
             self.ctx._check(self.ctx.lib.bm_rt_ray_queue_counts(self.h, _up(out), n.value, C.byref(n)))
         return out
 
+    def debugTileCosts(self, set=None, get: int = 0):
+        """bm_rt_debug_tile_costs, the test hook of the cost-ordered schedule: set (uint32 words) replaces the
+        head of this target's per-tile cost table, which the next trace sorts its tiles by; get = n returns the
+        table's first n words as a uint32 array once the target's stream has finished (None without get)."""
+        if set is not None:
+            a = np.ascontiguousarray(set, np.uint32).reshape(-1)
+            self.ctx._check(self.ctx.lib.bm_rt_debug_tile_costs(self.h, a.size, _up(a), None))
+        if not get:
+            return None
+        out = np.empty(int(get), np.uint32)
+        self.ctx._check(self.ctx.lib.bm_rt_debug_tile_costs(self.h, out.size, None, _up(out)))
+        return out
+
     def lastTiming(self):
         """Multi-device contexts: (band trace ms, exchange ms) of the last frame traced into this
         target, from HIP events (bm_rt_last_timing; waits for that frame)."""

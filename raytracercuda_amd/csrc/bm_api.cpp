@@ -561,6 +561,9 @@ int32_t bm_context_set_param(bm_context* ctx, uint32_t key, int64_t value) {
     if (key == BM_PARAM_TRACE_PRIO_LEVEL && value > 3) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: prio 0..3");
     if (key == BM_PARAM_CULL_DEPTH && (value == 0 || value > 2))
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: CULL_DEPTH is 1 or 2");
+    // a region of 2^16 tiles holds at most 2^22 rays: well inside the 32-bit region stride of the ray queue
+    if (key == BM_PARAM_CULL_TILES && value > (int64_t)1 << 16)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: CULL_TILES is at most 2^16");
     // k_front (one-launch gather + keys + top-digit pass) was removed in round 5
     if (key == BM_PARAM_FRONT_MAX_N && value > 0)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, "set_param: FRONT_MAX_N: k_front was removed (always 0)");
@@ -2670,6 +2673,31 @@ int32_t bm_debug_primitives(bm_context* ctx, uint32_t n, const float* in, float*
     din.release();
     dout.release();
     BM_HIP(ctx, e);
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_rt_debug_tile_costs(bm_rt* rt, uint32_t n, const uint32_t* set, uint32_t* get) {
+    if (!rt || !rt->ctx) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = rt->ctx;
+    if (ctx->multi() || n == 0 || (!set && !get))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "debug_tile_costs: single-device contexts, n > 0, set or get");
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = rt_stream(rt);
+    const size_t bytes = 4 * (size_t)n;
+    if (set) {
+        BM_HIP(ctx, rt_acquire(rt));
+        if (rt->tile_cost.cap < bytes) {  // as trace_impl grows it; the next trace finds room and fills nothing
+            BM_HIP(ctx, hipStreamSynchronize(st));
+            BM_HIP(ctx, rt->tile_cost.reserve(bytes));
+        }
+        BM_HIP(ctx, hipMemcpyAsync(rt->tile_cost.p, set, bytes, hipMemcpyHostToDevice, st));
+    }
+    if (get) {
+        if (rt->tile_cost.cap < bytes)
+            return fail(ctx, BM_ERROR_NOT_BUILT, "debug_tile_costs: the target's table holds fewer words");
+        BM_HIP(ctx, hipMemcpyAsync(get, rt->tile_cost.p, bytes, hipMemcpyDeviceToHost, st));
+    }
+    BM_HIP(ctx, hipStreamSynchronize(st));  // the host words are consumed / delivered on return
     return BM_ERROR_ALL_FINE;
 }
 

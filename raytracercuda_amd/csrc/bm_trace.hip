@@ -137,7 +137,10 @@ hipError_t launch_variant(const TraceParams& p, int variant, hipStream_t s, uint
                     break;
                 }
             }
-            [[fallthrough]];
+            // no ray queue (a frame beyond the 16-bit pixel packing, BVH2, the shadow queue): the quad case,
+            // never the packet case below — trace_impl reserved the quad kernel's overflow area, reports
+            // quads and applied no envelope check
+            return launch_variant<COUNT, SH, W>(p, TRACE_QUAD, s, grid);
         case TRACE_PACKET:
             // wave packets: BVH4 primary rays, non-counting (a packet's visit order is not the oracle's)
             if constexpr (W == 4 && SH == SH_NONE && !COUNT) {
@@ -199,7 +202,8 @@ bool trace_compact_layout(uint32_t width, uint32_t local_rows, uint32_t min_tpr,
                           uint32_t* tiles_per_region) {
     if (width == 0 || local_rows == 0 || width > 0xFFFFu || local_rows > 0xFFFFu) return false;
     const uint64_t ntiles = (uint64_t)((width + CULL_TILE - 1) / CULL_TILE) * ((local_rows + CULL_TILE - 1) / CULL_TILE);
-    uint64_t tpr = min_tpr >= 4 ? (min_tpr + 3) / 4 * 4 : 32;  // tiles per region (a multiple of the 4 waves; 32: C2 in flight +1.7 %, C3 +3.4 % over 16)
+    // (rounded in 64 bits: bm_context_set_param caps min_tpr at 2^16, and no 32-bit value may wrap to 0 here)
+    uint64_t tpr = min_tpr >= 4 ? ((uint64_t)min_tpr + 3) / 4 * 4 : 32;  // tiles per region (a multiple of the 4 waves; 32: C2 in flight +1.7 %, C3 +3.4 % over 16)
     while ((ntiles + tpr - 1) / tpr > CULL_MAX_REGIONS) tpr += 4;
     *tiles_per_region = (uint32_t)tpr;
     *regions = (uint32_t)((ntiles + tpr - 1) / tpr);

@@ -150,6 +150,7 @@ __device__ __forceinline__ bool trace_pixel(const TraceParams& p, STACK& st, uin
     uint32_t ibest = NO_TRI;
     int sp = 0;
     uint32_t next = p.num_tris ? 0u : EMPTY_REF;
+    if (COUNT && !p.num_tris) ++c_nodes;  // an empty scene: the all-empty root record orc_bvh_trace visits
     uint32_t iter = 0;
 
     for (;;) {

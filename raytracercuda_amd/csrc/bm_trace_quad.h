@@ -200,6 +200,7 @@ __device__ __forceinline__ void quad_closest(const TraceParams& p, const QS& st,
     // per leaf); the per-ray sequence of leaf tests, pops and node visits is trace_pixel's.
     int sp = 0;
     uint32_t next = p.num_tris ? 0u : EMPTY_REF;
+    if (COUNT && !p.num_tris && c == 0) ++cn;  // an empty scene: the all-empty root record orc_bvh_trace visits
     uint32_t iter = 0;
     for (;;) {
         prio_boost<PRIO>(p, iter);
@@ -606,8 +607,8 @@ __device__ __forceinline__ void cull_tiles(const TraceParams& p) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) enter |= child_hit(&cb[k][0], &cb[k][3], eye, inv, __builtin_inff(), tn);
                     }
-                    if (COUNT && !enter) ++cn;  // the root record the quad traversal would visit
                 }
+                if (COUNT && !enter) ++cn;  // the root record the quad traversal would visit (an empty scene's too)
                 // second level, decided for the wave's survivors only: tiles away from the model
                 // skip it on one scalar test
                 if (DEEP && ballot(enter)) {
