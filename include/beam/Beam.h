@@ -255,6 +255,13 @@ class IScene {
     u32 occluded(const bm_ray* deviceRays, u32 n, uint8_t* deviceOut, u32 flags = 0) {
         return (u32)bm_scene_trace_rays(h_, deviceRays, n, BM_RAYS_ANY_HIT, flags, deviceOut);
     }
+    // Extension: the k nearest hits of each ray in (t, id) order, k records per ray (bm_scene_trace_rays_multi;
+    // asynchronous on the context stream). deviceCounts (optional): the records that are hits; with
+    // flags = BM_MULTI_COUNT_ALL (deviceCounts required, k may be 0) every crossing within tmax.
+    u32 traceRaysMulti(const bm_ray* deviceRays, u32 n, u32 k, bm_hit* deviceHits, uint32_t* deviceCounts = nullptr,
+                       u32 flags = 0) {
+        return (u32)bm_scene_trace_rays_multi(h_, deviceRays, n, k, flags, deviceHits, deviceCounts);
+    }
     // Extension: the meshes' vertex slots interpolated at n hit records in device memory, up to
     // BM_ATTR_MAX_REQS requests per call (bm_scene_hit_attributes; asynchronous on the context stream).
     u32 hitAttributes(const bm_hit* deviceHits, u32 n, const bm_attr_req* reqs, u32 numReqs) {

@@ -330,6 +330,61 @@ int32_t bm_scene_trace_rays(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uin
 int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode,
                                      uint32_t flags, void* out_dev, uint64_t out[3]);
 
+/* ---- multi-hit ray queries: the k nearest hits of each ray, and hit counts --------------------
+ * What lies behind the first surface: the first k layers along a ray in order (transparency, X-ray
+ * views, depth peeling), entry/exit pairs (thickness, attenuation) and the number of crossings (its
+ * parity: inside or outside). One traversal per ray; no origin is moved, so coincident surfaces
+ * (a mesh added twice, two instances on one spot) are neither dropped nor counted twice.
+ * rays_dev and hits_dev are device pointers on the context's device, 16-byte aligned, counts_dev
+ * 4-byte aligned. The work is enqueued on the context stream and the call returns without waiting;
+ * bm_sync waits. On a multi-device context the query runs on the root device alone. dir need not be
+ * normalised: t is in units of dir.
+ * For ray i with origin o, direction d and tmax, H_i is the set of ALL triangles g of the scene that
+ *   the triangle function below accepts with 0 < t_g < FLT_MAX and t_g <= tmax (tmax = +inf:
+ *   unbounded), ordered by (t_g, g) ascending: equal t resolves to the lower global triangle id.
+ * The triangle function of o, d and the triangle's v0, e1 = v1 - v0, e2 = v2 - v0 (each one float32
+ *   subtraction per component), in float32, one rounding per operation in the order written, never
+ *   contracted; dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z; cross(a,b) = (a.y*b.z - b.y*a.z,
+ *   a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y); a comparison with NaN is false; the division is correctly
+ *   rounded; there is no determinant epsilon:
+ *     p = cross(d,e2)     det = dot(e1,p)     inv = 1 / det
+ *     tv = o - v0         u = dot(tv,p) * inv
+ *     u < 0 || u > 1      -> rejected
+ *     q = cross(tv,e1)    v = dot(d,q) * inv
+ *     v < 0 || v + u > 1  -> rejected
+ *     t = dot(e2,q) * inv
+ *   A NaN t is never accepted (0 < t is false). This is the closest-hit query's own test: record 0
+ *   below equals what BM_RAYS_CLOSEST writes for the same ray, bit for bit.
+ * hits_dev is bm_hit[n * k]. hits_dev[i*k + j] for j < min(k, |H_i|) is the j-th element of H_i as
+ *   {t, u, v, tri_id}; the remaining records of the ray's k are the miss record (t = +inf, u = v = 0,
+ *   tri_id = BM_NO_TRIANGLE). The n * k records feed bm_scene_hit_attributes as they are.
+ * Without BM_MULTI_COUNT_ALL: k is 1..BM_MULTI_MAX_HITS; counts_dev may be NULL, otherwise
+ *   counts_dev[i] = min(k, |H_i|). The traversal prunes by the k-th t once the list is full.
+ * With BM_MULTI_COUNT_ALL: counts_dev is required and counts_dev[i] = |H_i|, every crossing within
+ *   tmax; the traversal is pruned by tmax alone. k is 0..BM_MULTI_MAX_HITS; with k = 0 hits_dev may
+ *   be NULL and nothing is written to it (a pure crossing count).
+ * Invalid rays (a non-finite origin or direction component, tmax NaN or <= 0) are not traced: k miss
+ *   records, count 0. Over an empty built scene every ray misses.
+ * Rays are traced in the order given, 16 consecutive rays per wave, as by bm_scene_trace_rays. The
+ *   range note at bm_camera_trace (origins within BM_ENVELOPE_EXTENTS) applies unchanged: the box
+ *   test is the same.
+ * BM_ERROR_INVALID_PARAMETER: a null handle; with n > 0 a null rays_dev, a null hits_dev while k > 0,
+ * a null counts_dev with BM_MULTI_COUNT_ALL; a misaligned pointer; k out of range; an unknown flag
+ * bit; a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT: the scene has no
+ * current build. n = 0 succeeds without a launch. */
+#define BM_MULTI_MAX_HITS 16u
+#define BM_MULTI_COUNT_ALL 1u /* flags */
+int32_t bm_scene_trace_rays_multi(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t k,
+                                  uint32_t flags, bm_hit* hits_dev, uint32_t* counts_dev);
+/* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle tests (a
+ * leaf's triangle count per leaf reached), out[2] hit records written (the sum of min(k, |H_i|)) or,
+ * with BM_MULTI_COUNT_ALL, the sum of |H_i|; invalid rays count nothing. With k = 1 and no flag,
+ * out[0] and out[1] are those of bm_scene_trace_rays_counters in closest mode. Results are written
+ * exactly as bm_scene_trace_rays_multi writes them. Synchronous. */
+int32_t bm_scene_trace_rays_multi_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t k,
+                                           uint32_t flags, bm_hit* hits_dev, uint32_t* counts_dev,
+                                           uint64_t out[3]);
+
 /* ---- closest-point queries: the nearest triangle to each point of a batch ----------------------
  * For point i: which triangle of the scene is nearest, how far, and where on it — unsigned distance
  * fields, point-cloud-to-mesh losses, proximity tests, snapping and projecting points onto a surface.

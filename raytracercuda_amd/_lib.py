@@ -91,6 +91,8 @@ class Hit(C.Structure):
 
 
 RAYS_CLOSEST, RAYS_ANY_HIT = 0, 1
+MULTI_MAX_HITS = 16   # BM_MULTI_MAX_HITS: records per ray of bm_scene_trace_rays_multi
+MULTI_COUNT_ALL = 1   # its flag: count every crossing within tmax
 
 
 class Point(C.Structure):
@@ -172,6 +174,8 @@ SIGNATURES = {
     "bm_scene_destroy": (None, [_P]),
     "bm_scene_trace_rays": (_I, [_P, _P, _U, _U, _U, _P]),
     "bm_scene_trace_rays_counters": (_I, [_P, _P, _U, _U, _U, _P, _U64P]),
+    "bm_scene_trace_rays_multi": (_I, [_P, _P, _U, _U, _U, _P, _P]),
+    "bm_scene_trace_rays_multi_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _U64P]),
     "bm_scene_closest_points": (_I, [_P, _P, _U, _U, _P]),
     "bm_scene_closest_points_counters": (_I, [_P, _P, _U, _U, _P, _U64P]),
     "bm_scene_hit_attributes": (_I, [_P, _P, _U, C.POINTER(AttrReq), _U]),

@@ -417,6 +417,74 @@ class IScene:
             res["counters"] = cnt
         return res
 
+    def traceRaysMultiDevice(self, rays_ptr: int, n: int, k: int, hits_ptr: int, counts_ptr: int = 0, flags: int = 0,
+                             counters=None) -> int:
+        """bm_scene_trace_rays_multi on device pointers (n bm_ray records of 32 bytes in, n * k bm_hit records
+        of 16 bytes out, both 16-byte aligned; counts_ptr: n uint32, or 0); returns the error code.
+        Asynchronous on the context stream unless `counters` (a uint64[3] numpy array to fill) is given.
+        flags: MULTI_COUNT_ALL or 0."""
+        rp, hp, cp = C.c_void_p(rays_ptr or None), C.c_void_p(hits_ptr or None), C.c_void_p(counts_ptr or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_trace_rays_multi(self.h, rp, n, k, flags, hp, cp)
+        return self.ctx.lib.bm_scene_trace_rays_multi_counters(self.h, rp, n, k, flags, hp, cp,
+                                                               counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def traceRaysMulti(self, origins, dirs=None, tmax=None, k: int = 4, count_all: bool = False,
+                       counters: bool = False):
+        """The k nearest hits of each of n rays in (t, id) order (bm_scene_trace_rays_multi), k = 1..16, and
+        per ray "count": the records that are hits, or with count_all every crossing within tmax (k may then
+        be 0). Rays and tmax as for traceRays.
+
+        numpy in: uploads, traces and waits; returns numpy arrays {"t", "u", "v", "tri_id"} of shape (n, k) (a
+        miss slot: t = inf, tri_id = NO_TRIANGLE) and "count" (n,) uint32.
+        torch tensors on the context's device: nothing waits. Returns {"hits": (n, k, 4) float32, "t", "u", "v",
+        "tri_id" (views of hits, (n, k); tri_id as int32, -1 in a miss slot), "count": (n,) int32};
+        res["hits"].view(-1, 4) goes straight into hitAttributes as n * k hits.
+        counters=True adds "counters": [node records, triangle tests, the sum of the counts] (waits)."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        on_device = isinstance(origins, torch.Tensor)
+        if on_device:
+            if dirs is None:
+                rays = origins
+                if rays.dim() != 2 or rays.shape[1] != 8:
+                    raise BeamError(ERROR_INVALID_PARAMETER, "traceRaysMulti: packed rays are (n, 8) float32")
+            else:
+                rays = torch.zeros((origins.shape[0], 8), dtype=torch.float32, device=origins.device)
+                rays[:, 0:3] = origins
+                rays[:, 3] = float("inf") if tmax is None else tmax
+                rays[:, 4:7] = dirs
+            if rays.device != dev or rays.dtype != torch.float32 or not rays.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"traceRaysMulti: rays must be contiguous float32 on {dev} (the context's device)")
+        else:
+            o = _f32(origins).reshape(-1, 3)
+            packed = np.zeros((o.shape[0], 8), np.float32)
+            packed[:, 0:3] = o
+            packed[:, 3] = np.inf if tmax is None else tmax
+            packed[:, 4:7] = _f32(dirs).reshape(-1, 3)
+            rays = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = rays.shape[0]
+        out = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+        count = torch.empty((n,), dtype=torch.int32, device=dev)
+        cnt = np.zeros(3, np.uint64) if counters else None
+        self.ctx._check(self.traceRaysMultiDevice(rays.data_ptr() if n else 0, n, k, out.data_ptr() if n and k else 0,
+                                                  count.data_ptr() if n else 0,
+                                                  _lib.MULTI_COUNT_ALL if count_all else 0, cnt))
+        self._rays_keep = rays  # until the next query: the kernel may not have read them yet
+        if on_device:
+            res = {"hits": out, "t": out[..., 0], "u": out[..., 1], "v": out[..., 2],
+                   "tri_id": out.view(torch.int32)[..., 3], "count": count}
+        else:
+            self.ctx.sync()
+            h = out.cpu().numpy()
+            res = {"t": h[..., 0].copy(), "u": h[..., 1].copy(), "v": h[..., 2].copy(),
+                   "tri_id": h.view(np.uint32)[..., 3].copy(), "count": count.cpu().numpy().view(np.uint32)}
+        if counters:
+            res["counters"] = cnt
+        return res
+
     def closestPointsDevice(self, points_ptr: int, n: int, out_ptr: int, counters=None, flags=0) -> int:
         """bm_scene_closest_points on device pointers (n bm_point records of 16 bytes in, n bm_hit records of
         16 bytes out, both 16-byte aligned); returns the error code. Asynchronous on the context stream unless

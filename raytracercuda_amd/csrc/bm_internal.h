@@ -191,6 +191,10 @@ struct TraceParams {
     const float4* q_rays;
     void* q_out;
     uint32_t q_n;
+    // multi-hit ray queries (bm_multihit.hip): q_out holds q_k bm_hit records per ray; q_counts (may be null
+    // unless every crossing is counted) one count per ray
+    uint32_t q_k;
+    uint32_t* q_counts;
 };
 
 bool trace_variant_persistent(int variant);
@@ -222,6 +226,11 @@ hipError_t launch_query_rays(const TraceParams& p, uint32_t mode, bool count, hi
 // in p.q_rays, one bm_hit each into p.q_out; BVH4 scenes, set up as for launch_query_rays. count: into
 // p.counters[0..3] (node records, triangle evaluations, points with a result, the deepest stack held).
 hipError_t launch_closest_points(const TraceParams& p, bool count, hipStream_t s);
+// Multi-hit ray query (bm_multihit.hip): the p.q_k (t, id)-nearest hits of each of p.q_n rays into p.q_out, ray i's
+// at records i * q_k ..., and per ray into p.q_counts the records that are hits or, with count_all (q_counts
+// required, q_k may be 0), every triangle crossed within tmax; set up as for launch_query_rays. count: into
+// p.counters[0..2] (node records, triangle tests, the sum of the per-ray counts).
+hipError_t launch_query_multi(const TraceParams& p, bool count_all, bool count, hipStream_t s);
 // ---- hit attributes (bm_attrs.hip): vertex slots interpolated at the hits of a ray query ------------
 // One entry per scene mesh, in scene order: every slot's device buffer (null: the mesh has none), so the
 // table depends on the meshes alone and not on what a call requests.
