@@ -273,6 +273,13 @@ class IScene {
     u32 closestPoints(const bm_point* devicePoints, u32 n, bm_hit* deviceHits) {
         return (u32)bm_scene_closest_points(h_, devicePoints, n, 0, deviceHits);
     }
+    // Extension: the k nearest triangles within each point's rmax in (distance, id) order, k records per point
+    // (bm_scene_closest_points_multi; asynchronous on the context stream). deviceCounts (optional): the records
+    // written; with flags = BM_MULTI_COUNT_ALL (deviceCounts required, k may be 0) every triangle within rmax.
+    u32 closestPointsMulti(const bm_point* devicePoints, u32 n, u32 k, u32 flags, bm_hit* deviceHits,
+                           uint32_t* deviceCounts = nullptr) {
+        return (u32)bm_scene_closest_points_multi(h_, devicePoints, n, k, flags, deviceHits, deviceCounts);
+    }
     // Extension: instance transforms (include/beam_c.h, "instance transforms"). xform: 12 floats, row-major
     // 3x4 (xformFromColumnMajor4x4 converts a glm::mat4's 16 floats). addInstance appends the mesh at that
     // placement and reports the entry's index; setInstanceTransform takes effect at the next updateGPUScene

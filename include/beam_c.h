@@ -443,6 +443,50 @@ int32_t bm_scene_closest_points(bm_scene* s, const bm_point* points_dev, uint32_
 int32_t bm_scene_closest_points_counters(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t flags,
                                          bm_hit* out_dev, uint64_t out[4]);
 
+/* ---- multi-result point queries: the k nearest triangles to each point, and how many lie within r
+ * The point side's counterpart of bm_scene_trace_rays_multi. For point i: all triangles within rmax,
+ * each with its closest point (the contact set of a sphere collider: with bm_scene_hit_attributes the
+ * contact point and normal per triangle, the penetration depth rmax - t); the k nearest triangles
+ * (robust normals and signs near edges and creases, where the single nearest triangle is arbitrary
+ * among several at equal distance; blended distance fields; point-cloud-to-mesh losses with more than
+ * one candidate); and the number of triangles within rmax (a density or "is anything near" probe
+ * that writes no records, or the size of a second pass). One traversal per point.
+ * points_dev and hits_dev are device pointers on the context's device, 16-byte aligned, counts_dev
+ * 4-byte aligned. The work is enqueued on the context stream and the call returns without waiting;
+ * bm_sync waits. On a multi-device context the query runs on the root device alone.
+ * For point i with p and rmax, N_i is the set of ALL triangles g of the scene whose dd_g is not NaN
+ *   and dd_g <= rmax*rmax (one float32 multiply; rmax = +inf: unbounded), ordered by (dd_g, g)
+ *   ascending: equal distance resolves to the lower global triangle id. dd_g, u and v are the
+ *   closest-point section's function of p and the triangle, as stated there.
+ * hits_dev is bm_hit[n * k]. hits_dev[i*k + j] for j < min(k, |N_i|) is the j-th element of N_i as
+ *   {t = sqrtf(dd), u, v, tri_id} in bm_scene_closest_points' convention; the remaining records of the
+ *   point's k are the miss record (t = +inf, u = v = 0, tri_id = BM_NO_TRIANGLE). The n * k records
+ *   feed bm_scene_hit_attributes as they are.
+ * Without BM_MULTI_COUNT_ALL: k is 1..BM_MULTI_MAX_HITS; counts_dev may be NULL, otherwise
+ *   counts_dev[i] = min(k, |N_i|). With k = 1, record 0 equals what bm_scene_closest_points writes
+ *   for the same point, bit for bit.
+ * With BM_MULTI_COUNT_ALL: counts_dev is required and counts_dev[i] = |N_i|, every triangle within
+ *   rmax. k is 0..BM_MULTI_MAX_HITS; with k = 0 hits_dev may be NULL and nothing is written to it (a
+ *   pure count).
+ * Invalid points (a non-finite component of p; rmax NaN or <= 0) are not looked up: k miss records,
+ *   count 0. Over an empty built scene every point misses.
+ * Points are taken in the order given, 16 consecutive points per wave, as by bm_scene_closest_points.
+ * BM_ERROR_INVALID_PARAMETER: a null handle; with n > 0 a null points_dev, a null hits_dev while
+ * k > 0, a null counts_dev with BM_MULTI_COUNT_ALL; a misaligned pointer; k out of range; an unknown
+ * flag bit; a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT: the scene has no
+ * current build. n = 0 succeeds without a launch. */
+int32_t bm_scene_closest_points_multi(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t k,
+                                      uint32_t flags, bm_hit* hits_dev, uint32_t* counts_dev);
+/* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle evaluations (a
+ * leaf's triangle count per leaf reached), out[2] records written (the sum of min(k, |N_i|)) or, with
+ * BM_MULTI_COUNT_ALL, the sum of |N_i|, out[3] the largest number of stack entries any query held at
+ * once; invalid points count nothing. With k = 1 and no flag, out[0] and out[1] are those of
+ * bm_scene_closest_points_counters. Results are written exactly as bm_scene_closest_points_multi
+ * writes them. Synchronous. */
+int32_t bm_scene_closest_points_multi_counters(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t k,
+                                               uint32_t flags, bm_hit* hits_dev, uint32_t* counts_dev,
+                                               uint64_t out[4]);
+
 /* ---- hit attributes: the meshes' vertex slots interpolated at ray-query hits ------------------
  * The reference's bmFaceInterpolate<T>(face, u, v, meshData, dataIdx) (CudaComon.cuh:253-266) over n
  * bm_hit records in device memory (as bm_scene_trace_rays writes them, or made by the caller): what a

@@ -91,8 +91,9 @@ class Hit(C.Structure):
 
 
 RAYS_CLOSEST, RAYS_ANY_HIT = 0, 1
-MULTI_MAX_HITS = 16   # BM_MULTI_MAX_HITS: records per ray of bm_scene_trace_rays_multi
-MULTI_COUNT_ALL = 1   # its flag: count every crossing within tmax
+MULTI_MAX_HITS = 16   # BM_MULTI_MAX_HITS: records per ray of bm_scene_trace_rays_multi (per point of
+                      # bm_scene_closest_points_multi)
+MULTI_COUNT_ALL = 1   # their flag: count every crossing within tmax (every triangle within rmax)
 
 
 class Point(C.Structure):
@@ -178,6 +179,8 @@ SIGNATURES = {
     "bm_scene_trace_rays_multi_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _U64P]),
     "bm_scene_closest_points": (_I, [_P, _P, _U, _U, _P]),
     "bm_scene_closest_points_counters": (_I, [_P, _P, _U, _U, _P, _U64P]),
+    "bm_scene_closest_points_multi": (_I, [_P, _P, _U, _U, _U, _P, _P]),
+    "bm_scene_closest_points_multi_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _U64P]),
     "bm_scene_hit_attributes": (_I, [_P, _P, _U, C.POINTER(AttrReq), _U]),
     "bm_camera_create": (_I, [_P, C.POINTER(_P)]),
     "bm_camera_set_initial_rays": (_I, [_P, _U, _U, _F, _F, _F, _F, _F]),

@@ -485,6 +485,73 @@ class IScene:
             res["counters"] = cnt
         return res
 
+    def closestPointsMultiDevice(self, points_ptr: int, n: int, k: int, hits_ptr: int, counts_ptr: int = 0,
+                                 flags: int = 0, counters=None) -> int:
+        """bm_scene_closest_points_multi on device pointers (n bm_point records of 16 bytes in, n * k bm_hit
+        records of 16 bytes out, both 16-byte aligned; counts_ptr: n uint32, or 0); returns the error code.
+        Asynchronous on the context stream unless `counters` (a uint64[4] numpy array to fill) is given.
+        flags: MULTI_COUNT_ALL or 0."""
+        pp, hp, cp = C.c_void_p(points_ptr or None), C.c_void_p(hits_ptr or None), C.c_void_p(counts_ptr or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_closest_points_multi(self.h, pp, n, k, flags, hp, cp)
+        return self.ctx.lib.bm_scene_closest_points_multi_counters(self.h, pp, n, k, flags, hp, cp,
+                                                                   counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def closestPointsMulti(self, points, rmax=None, k: int = 4, count_all: bool = False, counters: bool = False):
+        """The k nearest triangles within rmax of each of n points in (distance, id) order
+        (bm_scene_closest_points_multi), k = 1..16, and per point "count": the records written, or with
+        count_all every triangle within rmax (k may then be 0). Points and rmax as for closestPoints.
+
+        numpy in: uploads, queries and waits; returns numpy arrays {"t", "u", "v", "tri_id"} of shape (n, k) (a
+        miss slot: t = inf, tri_id = NO_TRIANGLE) and "count" (n,) uint32.
+        torch tensors on the context's device: nothing waits. Returns {"hits": (n, k, 4) float32, "t", "u", "v",
+        "tri_id" (views of hits, (n, k); tri_id as int32, -1 in a miss slot), "count": (n,) int32};
+        res["hits"].view(-1, 4) goes straight into hitAttributes as n * k hits.
+        counters=True adds "counters": [node records, triangle evaluations, the sum of the counts, deepest
+        stack] (waits)."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        on_device = isinstance(points, torch.Tensor)
+        if on_device:
+            if points.dim() == 2 and points.shape[1] == 4 and rmax is None:
+                pts = points
+            elif points.dim() == 2 and points.shape[1] == 3:
+                pts = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+                pts[:, 0:3] = points
+                pts[:, 3] = float("inf") if rmax is None else rmax
+            else:
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                "closestPointsMulti: points are (n, 3), or packed (n, 4), float32")
+            if pts.device != dev or pts.dtype != torch.float32 or not pts.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"closestPointsMulti: points must be contiguous float32 on {dev} (the context's device)")
+        else:
+            q = _f32(points).reshape(-1, 3)
+            packed = np.zeros((q.shape[0], 4), np.float32)
+            packed[:, 0:3] = q
+            packed[:, 3] = np.inf if rmax is None else rmax
+            pts = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = pts.shape[0]
+        out = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+        count = torch.empty((n,), dtype=torch.int32, device=dev)
+        cnt = np.zeros(4, np.uint64) if counters else None
+        self.ctx._check(self.closestPointsMultiDevice(pts.data_ptr() if n else 0, n, k,
+                                                      out.data_ptr() if n and k else 0, count.data_ptr() if n else 0,
+                                                      _lib.MULTI_COUNT_ALL if count_all else 0, cnt))
+        self._points_keep = pts  # until the next query: the kernel may not have read them yet
+        if on_device:
+            res = {"hits": out, "t": out[..., 0], "u": out[..., 1], "v": out[..., 2],
+                   "tri_id": out.view(torch.int32)[..., 3], "count": count}
+        else:
+            self.ctx.sync()
+            h = out.cpu().numpy()
+            res = {"t": h[..., 0].copy(), "u": h[..., 1].copy(), "v": h[..., 2].copy(),
+                   "tri_id": h.view(np.uint32)[..., 3].copy(), "count": count.cpu().numpy().view(np.uint32)}
+        if counters:
+            res["counters"] = cnt
+        return res
+
     def closestPointsDevice(self, points_ptr: int, n: int, out_ptr: int, counters=None, flags=0) -> int:
         """bm_scene_closest_points on device pointers (n bm_point records of 16 bytes in, n bm_hit records of
         16 bytes out, both 16-byte aligned); returns the error code. Asynchronous on the context stream unless

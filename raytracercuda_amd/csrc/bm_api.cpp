@@ -1990,21 +1990,23 @@ int32_t bm_scene_closest_points_counters(bm_scene* s, const bm_point* points_dev
     return query_impl(s, true, points_dev, n, 0, flags, out_dev, out);
 }
 
-// ---- multi-hit ray queries (bm_multihit.hip) -----------------------------------------------------
+// ---- multi-result queries: rays (bm_multihit.hip) and points (bm_points_multi.hip) ---------------
 // query_impl's path and order of checks with the k / flags pair in the mode's place: hits_dev holds k
-// records per ray and is not read for k = 0, counts_dev is required only when every crossing is counted.
-static int32_t multi_impl(bm_scene* s, const bm_ray* rays, uint32_t n, uint32_t k, uint32_t flags, bm_hit* hits,
-                          uint32_t* counts, uint64_t* counters) {
+// records per ray or point and is not read for k = 0, counts_dev is required only when everything within
+// the bound is counted. points: `rays` are bm_point records and the counters 4 words.
+static int32_t multi_impl(bm_scene* s, bool points, const void* rays, uint32_t n, uint32_t k, uint32_t flags,
+                          bm_hit* hits, uint32_t* counts, uint64_t* counters) {
     if (!s) return BM_ERROR_INVALID_PARAMETER;
     bm_context* ctx = s->ctx;
-    const std::string who = "trace_rays_multi: ";
+    const std::string who = points ? "closest_points_multi: " : "trace_rays_multi: ";
+    const std::string what = points ? "point" : "ray";  // the ray query's messages are the ones it had
     const bool all = (flags & BM_MULTI_COUNT_ALL) != 0;
     if (n && (!rays || (k && !hits) || (all && !counts)))
-        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "null ray, hit or count pointer");
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "null " + what + ", hit or count pointer");
     if (((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) & 15u) ||
         (reinterpret_cast<uintptr_t>(counts) & 3u))
         return fail(ctx, BM_ERROR_INVALID_PARAMETER,
-                    who + "ray and hit pointers must be 16-byte aligned, the count pointer 4-byte");
+                    who + what + " and hit pointers must be 16-byte aligned, the count pointer 4-byte");
     if ((flags & ~BM_MULTI_COUNT_ALL) || k > BM_MULTI_MAX_HITS || (k == 0 && !all))
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "k out of range or unknown flag bits");
     if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
@@ -2012,7 +2014,8 @@ static int32_t multi_impl(bm_scene* s, const bm_ray* rays, uint32_t n, uint32_t 
     if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
     if (s->kd || s->hash || s->width != 4)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
-    if (counters) std::fill(counters, counters + 3, uint64_t(0));
+    const int words = points ? 4 : 3;
+    if (counters) std::fill(counters, counters + words, uint64_t(0));
     if (n == 0) return BM_ERROR_ALL_FINE;
     BM_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
@@ -2035,25 +2038,37 @@ static int32_t multi_impl(bm_scene* s, const bm_ray* rays, uint32_t n, uint32_t 
         BM_HIP(ctx, hipMemsetAsync(ctx->rays_counters, 0, 4 * sizeof(unsigned long long), st));
         p.counters = ctx->rays_counters;
     }
-    BM_HIP(ctx, bm::launch_query_multi(p, all, counters != nullptr, st));
+    BM_HIP(ctx, points ? bm::launch_closest_points_multi(p, all, counters != nullptr, st)
+                       : bm::launch_query_multi(p, all, counters != nullptr, st));
     if (counters) {
         unsigned long long h[4];
         BM_HIP(ctx, hipMemcpyAsync(h, ctx->rays_counters, sizeof(h), hipMemcpyDeviceToHost, st));
         BM_HIP(ctx, hipStreamSynchronize(st));
-        std::copy(h, h + 3, counters);
+        std::copy(h, h + words, counters);
     }
     return BM_ERROR_ALL_FINE;
 }
 
 int32_t bm_scene_trace_rays_multi(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t k, uint32_t flags,
                                   bm_hit* hits_dev, uint32_t* counts_dev) {
-    return multi_impl(s, rays_dev, n, k, flags, hits_dev, counts_dev, nullptr);
+    return multi_impl(s, false, rays_dev, n, k, flags, hits_dev, counts_dev, nullptr);
 }
 
 int32_t bm_scene_trace_rays_multi_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t k, uint32_t flags,
                                            bm_hit* hits_dev, uint32_t* counts_dev, uint64_t out[3]) {
     if (!out) return BM_ERROR_INVALID_PARAMETER;
-    return multi_impl(s, rays_dev, n, k, flags, hits_dev, counts_dev, out);
+    return multi_impl(s, false, rays_dev, n, k, flags, hits_dev, counts_dev, out);
+}
+
+int32_t bm_scene_closest_points_multi(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t k, uint32_t flags,
+                                      bm_hit* hits_dev, uint32_t* counts_dev) {
+    return multi_impl(s, true, points_dev, n, k, flags, hits_dev, counts_dev, nullptr);
+}
+
+int32_t bm_scene_closest_points_multi_counters(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t k,
+                                               uint32_t flags, bm_hit* hits_dev, uint32_t* counts_dev, uint64_t out[4]) {
+    if (!out) return BM_ERROR_INVALID_PARAMETER;
+    return multi_impl(s, true, points_dev, n, k, flags, hits_dev, counts_dev, out);
 }
 
 // ---- hit attributes (bm_attrs.hip) ---------------------------------------------------------------

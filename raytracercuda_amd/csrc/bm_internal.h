@@ -192,7 +192,8 @@ struct TraceParams {
     void* q_out;
     uint32_t q_n;
     // multi-hit ray queries (bm_multihit.hip): q_out holds q_k bm_hit records per ray; q_counts (may be null
-    // unless every crossing is counted) one count per ray
+    // unless every crossing is counted) one count per ray. Multi-result point queries (bm_points_multi.hip):
+    // the same two per point
     uint32_t q_k;
     uint32_t* q_counts;
 };
@@ -231,6 +232,12 @@ hipError_t launch_closest_points(const TraceParams& p, bool count, hipStream_t s
 // required, q_k may be 0), every triangle crossed within tmax; set up as for launch_query_rays. count: into
 // p.counters[0..2] (node records, triangle tests, the sum of the per-ray counts).
 hipError_t launch_query_multi(const TraceParams& p, bool count_all, bool count, hipStream_t s);
+// Multi-result point query (bm_points_multi.hip): the p.q_k (dd, id)-nearest triangles within rmax of each of
+// p.q_n points (one float4 (p, rmax) each in p.q_rays) into p.q_out, point i's at records i * q_k ..., and per
+// point into p.q_counts the records written or, with count_all (q_counts required, q_k may be 0), every
+// triangle within rmax; set up as for launch_closest_points. count: into p.counters[0..3] (node records,
+// triangle evaluations, the sum of the per-point counts, the deepest stack held).
+hipError_t launch_closest_points_multi(const TraceParams& p, bool count_all, bool count, hipStream_t s);
 // ---- hit attributes (bm_attrs.hip): vertex slots interpolated at the hits of a ray query ------------
 // One entry per scene mesh, in scene order: every slot's device buffer (null: the mesh has none), so the
 // table depends on the meshes alone and not on what a call requests.

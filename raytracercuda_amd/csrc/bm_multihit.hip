@@ -15,125 +15,10 @@
 // quad_visit takes it as its tmax and the pop skips entries beyond it, both inclusive, so a triangle
 // tying the last entry's t with a lower id is still found. With k = 1 and no count-all the per-ray
 // sequence of node visits, leaf tests and pops is quad_closest's (the tests compare the counters).
-#include "bm_trace_quad.h"
+#include "bm_query_dev.h"
 
 namespace bm {
 namespace {
-
-constexpr int MULTI_CAP_SMALL = 4, MULTI_CAP_LARGE = BM_MULTI_MAX_HITS;
-static_assert(MULTI_CAP_LARGE == 16, "the list layout rotates within 16 slots of 16 bytes");
-// waves per SIMD the registers must allow. Small lists: the quad kernels' 7. Large lists: 12 KB of stack
-// and 16 KB of list per workgroup make five workgroups per CU (160 KB), so the registers need no more.
-constexpr int MULTI_WAVES_LARGE = 5;
-
-constexpr int QP_ROT = 0x93;  // quad_perm [3,0,1,2]: lane c reads lane c - 1, lane 0 reads lane 3
-
-__device__ __forceinline__ bool finite3(const vec3f a) {
-    return fabsf(a.x) < __builtin_inff() && fabsf(a.y) < __builtin_inff() && fabsf(a.z) < __builtin_inff();
-}
-
-template <int CTRL>
-__device__ __forceinline__ float4 dpp_f4(const float4 e) {
-    return make_float4(dpp_f<CTRL>(e.x), dpp_f<CTRL>(e.y), dpp_f<CTRL>(e.z), dpp_f<CTRL>(e.w));
-}
-
-__device__ __forceinline__ uint32_t quad_sum(uint32_t v) {
-    v += dpp_u<QP_X1>(v);
-    v += dpp_u<QP_X2>(v);
-    return v;
-}
-
-// Lexicographic (t, id) minimum of the quad's candidates: quad_min_hit without the barycentrics, which stay
-// with their owner lane until it writes the list entry.
-template <int CTRL>
-__device__ __forceinline__ void quad_min_tid_step(float& t, uint32_t& id) {
-    const float ot = dpp_f<CTRL>(t);
-    const uint32_t oid = dpp_u<CTRL>(id);
-    const bool take = ot < t || (ot == t && oid < id);
-    t = take ? ot : t;
-    id = take ? oid : id;
-}
-__device__ __forceinline__ void quad_min_tid(float& t, uint32_t& id) {
-    quad_min_tid_step<QP_X1>(t, id);
-    quad_min_tid_step<QP_X2>(t, id);
-}
-
-// (t, id) order of two entries
-__device__ __forceinline__ bool hit_below(float t, uint32_t id, float ot, uint32_t oid) {
-    return t < ot || (t == ot && id < oid);
-}
-
-// Per-ray sorted list of a quad: LDS [ray][CAP] of 16-B entries (t, u, v, id bits: the bm_hit image),
-// entry j of ray r in slot (j + 4r) mod CAP of r's row. ds_read_b128 serves a wave in four groups of four
-// quads ({0,3,5,6}, {1,2,4,7} and the same + 8) over 16 slots of 16 B per bank row: with CAP = 16 the
-// quad's lanes read slots 4(s + q) + c of their rows, with CAP = 4 slots 4q + c of the bank row — each
-// group's 16 lanes on 16 different slots either way, and the 8-lane groups of ds_write_b128 (two adjacent
-// quads, 8 slots per 128-B bank row) likewise. Unrotated, [ray][16] puts the four quads of a group on
-// the same four slots and [k][ray] the four lanes of a quad on one: both four-way conflicts.
-// BM_MULTI_LAYOUT (A/B builds, tools/multihit_bench.py): 1 = [k][ray], 2 = [ray][CAP] unrotated.
-#ifndef BM_MULTI_LAYOUT
-#define BM_MULTI_LAYOUT 0
-#endif
-template <int CAP>
-struct HitList {
-    float4* s;  // QRAYS * CAP entries
-    int ray;
-    __device__ __forceinline__ float4& at(uint32_t j) const {
-#if BM_MULTI_LAYOUT == 1
-        return s[j * QRAYS + (uint32_t)ray];
-#elif BM_MULTI_LAYOUT == 2
-        return s[(uint32_t)ray * CAP + j];
-#else
-        return s[(uint32_t)ray * CAP + ((j + 4u * (uint32_t)ray) & (uint32_t)(CAP - 1))];
-#endif
-    }
-};
-
-// Inserts the quad's candidate (t, id) — every lane holds the pair, the lane `owner` also its u, v — into
-// the list of cnt (<= k) entries, dropping the last entry of a full list; a candidate at or beyond
-// position k changes nothing. The owner writes the new entry, lane j mod 4 the shifted entry j. tlast: the
-// t of entry k - 1 once the list is full.
-template <int CAP>
-__device__ __forceinline__ void list_insert(const HitList<CAP>& hl, int c, uint32_t k, uint32_t& cnt, float t,
-                                            uint32_t id, bool owner, float u, float v, float& tlast) {
-    constexpr int STEPS = CAP / 4;
-    const float4 none = make_float4(__builtin_inff(), 0.f, 0.f, u2f(NO_TRI));
-    float4 e[STEPS];
-    uint32_t below = 0;
-#pragma unroll
-    for (int s = 0; s < STEPS; ++s) {
-        const uint32_t j = (uint32_t)c + 4u * s;
-        e[s] = none;
-        if (j < cnt) {
-            e[s] = hl.at(j);
-            below += hit_below(e[s].x, f2u(e[s].w), t, id) ? 1u : 0u;
-        }
-    }
-    const uint32_t pos = quad_sum(below);
-    if (pos >= k) return;
-    const uint32_t ncnt = min(cnt + 1u, k);
-    float4 carry = none;
-    float lt = pos + 1u == k ? t : -__builtin_inff();
-#pragma unroll
-    for (int s = 0; s < STEPS; ++s) {
-        const uint32_t j = (uint32_t)c + 4u * s;
-        const float4 left = dpp_f4<QP_ROT>(e[s]);
-        // old[j - 1]; selected per component (a select of whole float4s goes through private memory)
-        const float4 prev = make_float4(c == 0 ? carry.x : left.x, c == 0 ? carry.y : left.y, c == 0 ? carry.z : left.z,
-                                        c == 0 ? carry.w : left.w);
-        carry = left;
-        if (j > pos && j < ncnt) {
-            hl.at(j) = prev;
-            if (j + 1u == k) lt = prev.x;  // entry k - 1 is the new one or a shifted one: pos < k
-        }
-    }
-    if (owner) hl.at(pos) = make_float4(t, u, v, u2f(id));
-    cnt = ncnt;
-    if (ncnt == k) {
-        lt = fmaxf(lt, dpp_f<QP_X1>(lt));
-        tlast = fmaxf(lt, dpp_f<QP_X2>(lt));
-    }
-}
 
 // The k nearest hits of one ray over the quad, and with ALL the number of accepted triangles. One
 // iteration is quad_closest's: the pending leaf, the pop that follows it, the node visit(s).

@@ -10,86 +10,10 @@
 // distance found so far. The widening makes the pruning conservative against the rounding of the
 // triangle function, so the result is the lexicographic minimum of (dd, id) over ALL triangles, bit for
 // bit what an exhaustive evaluation of tri_nearest gives.
-#include "bm_trace_quad.h"
+#include "bm_query_dev.h"
 
 namespace bm {
 namespace {
-
-__device__ __forceinline__ bool finite3(const vec3f a) {
-    return fabsf(a.x) < __builtin_inff() && fabsf(a.y) < __builtin_inff() && fabsf(a.z) < __builtin_inff();
-}
-
-// The closest point of one 48-B triangle record (v0 | id, e1, e2) to p: Ericson's seven regions (vertex
-// v0, vertex v1, edge v0v1, vertex v2, edge v0v2, edge v1v2, interior; the first match wins) in float32,
-// one rounding per operation in the order written (include/beam_c.h states it; the tests restate it). dd
-// is the squared distance, (u, v) the barycentrics in the hit-attribute convention: the point is
-// v0*(1-(u+v)) + v1*u + v2*v. The regions are chosen by selects in reverse order, so a later (earlier
-// listed) match overrides; every region that divides does so once, through num / den. Where that
-// division is 0/0 or 1/0 (a zero-area triangle outside its vertex regions) dd is NaN and never a candidate.
-__device__ __forceinline__ void tri_nearest(const float4 a, const float4 b, const float4 cc, const vec3f p, float& dd,
-                                            float& u, float& v) {
-    const vec3f e1 = v3(b.x, b.y, b.z), e2 = v3(cc.x, cc.y, cc.z);
-    const vec3f ap = sub(p, v3(a.x, a.y, a.z));
-    const float d1 = dot(e1, ap), d2 = dot(e2, ap);
-    const float a11 = dot(e1, e1), a12 = dot(e1, e2), a22 = dot(e2, e2);
-    const float d3 = d1 - a11, d4 = d2 - a12, d5 = d1 - a12, d6 = d2 - a22;
-    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-    const float s = d4 - d3, r = d5 - d6;
-    int reg = 7;
-    float num = 1.0f, den = (va + vb) + vc;
-    if (va <= 0.0f && s >= 0.0f && r >= 0.0f) reg = 6, num = s, den = s + r;
-    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) reg = 5, num = d2, den = d2 - d6;
-    if (d6 >= 0.0f && d5 <= d6) reg = 4;
-    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) reg = 3, num = d1, den = d1 - d3;
-    if (d3 >= 0.0f && d4 <= d3) reg = 2;
-    if (d1 <= 0.0f && d2 <= 0.0f) reg = 1;
-    const float w = num / den;
-    u = reg == 2 ? 1.0f : reg == 3 ? w : reg == 6 ? 1.0f - w : reg == 7 ? vb * w : 0.0f;
-    v = reg == 4 ? 1.0f : (reg == 5 || reg == 6) ? w : reg == 7 ? vc * w : 0.0f;
-    const vec3f q = v3(ap.x - (e1.x * u + e2.x * v), ap.y - (e1.y * u + e2.y * v), ap.z - (e1.z * u + e2.z * v));
-    dd = dot(q, q);
-}
-
-// The pruning bound for a best squared distance: (sqrt(best) + m)^2, never below best itself (its own
-// rounding could otherwise land an ulp under a huge rmax^2). m absorbs what rounding can put a triangle's
-// dd below the squared distance to a box that contains the triangle.
-__device__ __forceinline__ float widen(float best, float m) {
-    const float s = sqrtf(best) + m;
-    return fmaxf(s * s, best);
-}
-
-// Node step of the nearest-triangle traversal: lane c loads child c of the 128-B record as quad_visit
-// does and takes the squared distance from pt to its box (per axis max(lo - p, p - hi, 0), squared,
-// summed in dot order). A child within `bound` is kept; the kept ones are ranked by order_key(boxdd, c)
-// with quad_visit's DPP exchange, ranks 1..nh-1 pushed farthest first with boxdd as their stack key, the
-// nearest returned to all four lanes (EMPTY_REF when none is kept). An empty slot (EMPTY_REF; its NaN
-// box would read as distance 0 through fmaxf) is never kept.
-template <typename QS>
-__device__ __forceinline__ uint32_t nearest_visit(const TraceParams& p, uint32_t node, int c, const vec3f pt,
-                                                  float bound, const QS& st, int& sp) {
-    const uint32_t* nd = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(p.nodes) +
-                                                           ((node << 7) | ((uint32_t)c << 2)));
-    const float lx = u2f(nd[0]), ly = u2f(nd[4]), lz = u2f(nd[8]);
-    const float hx = u2f(nd[12]), hy = u2f(nd[16]), hz = u2f(nd[20]);
-    const uint32_t ref = nd[24];
-    const float dx = fmaxf(fmaxf(lx - pt.x, pt.x - hx), 0.0f);
-    const float dy = fmaxf(fmaxf(ly - pt.y, pt.y - hy), 0.0f);
-    const float dz = fmaxf(fmaxf(lz - pt.z, pt.z - hz), 0.0f);
-    const float boxdd = (dx * dx + dy * dy) + dz * dz;
-    const bool h = (ref != EMPTY_REF) & (boxdd <= bound);
-    const uint32_t key = h ? order_key(boxdd, (uint32_t)c) : ~0u;
-    const uint32_t k1 = dpp_u<QP_X1>(key), k2 = dpp_u<QP_X2>(key), k3 = dpp_u<QP_X3>(key);
-    const uint32_t rank = (uint32_t)(k1 < key) + (uint32_t)(k2 < key) + (uint32_t)(k3 < key);
-    uint32_t nh = h ? 4u : rank;  // a dropped child's key ~0u ranks after every kept one: its rank is their count
-    nh = min(nh, dpp_u<QP_X1>(nh));
-    nh = min(nh, dpp_u<QP_X2>(nh));
-    if (h && rank > 0) st.put(sp + (int)(nh - 1u - rank), ref, boxdd);
-    sp += max((int)nh - 1, 0);
-    uint32_t nx = (h && rank == 0) ? ref : EMPTY_REF;
-    nx = min(nx, dpp_u<QP_X1>(nx));
-    nx = min(nx, dpp_u<QP_X2>(nx));
-    return nx;
-}
 
 // Nearest triangle of one point over the quad: the lexicographic minimum of (dd, id) over the triangles
 // with dd <= best on entry (rmax^2). One iteration is quad_closest's: the pending leaf, the pop that
