@@ -9,7 +9,10 @@ Outputs : tests/golden/meshes/{bunny,suzanne,f16}.npz      — mesh arrays (inpu
 
 Expected frames come from the oracle's restatement of the reference (kd-tree + march,
 oracle/beam_oracle.c), which this script first checks against the known answers SURVEY.md §8(c)
-recorded from the reference's own CPU-emulation path. It also records, per view, the pixels where
+recorded from the reference's own CPU-emulation path. The restatement itself is pinned pixel by pixel
+(packed colour, triangle id, tree statistics; not t, which the reference does not write) to frames that
+path computes: tests/golden/make_ref_frames.py -> tests/golden/ref, tests/test_oracle_ref_frames.py. If
+that pin ever makes the restatement change, regenerate the goldens here. It also records, per view, the pixels where
 the reference's first-hit-leaf early-out (BuildTree.cu:427-431) returns a different triangle than
 the true closest hit, with the closest-hit answer (the HIP path computes closest hit).
 """
