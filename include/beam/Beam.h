@@ -248,7 +248,8 @@ class IScene {
     u32 refitGPUScene(bm_build_stats* stats = nullptr) { return (u32)bm_scene_refit(h_, stats); }
     // Extension: ray queries over n rays in device memory (bm_scene_trace_rays; asynchronous on the
     // context stream). traceRays: the closest hit within each ray's tmax; occluded: one byte per ray,
-    // 1 when anything lies on the segment origin -> origin + dir. flags: none defined yet (0).
+    // 1 when anything lies on the segment origin -> origin + dir. flags: 0 or the filter bits
+    // BM_RAYS_CULL_* / BM_RAYS_PAD_* (face culling; pad as a triangle to skip, a tmin or a ray mask).
     u32 traceRays(const bm_ray* deviceRays, u32 n, bm_hit* deviceHits, u32 flags = 0) {
         return (u32)bm_scene_trace_rays(h_, deviceRays, n, BM_RAYS_CLOSEST, flags, deviceHits);
     }
@@ -257,7 +258,8 @@ class IScene {
     }
     // Extension: the k nearest hits of each ray in (t, id) order, k records per ray (bm_scene_trace_rays_multi;
     // asynchronous on the context stream). deviceCounts (optional): the records that are hits; with
-    // flags = BM_MULTI_COUNT_ALL (deviceCounts required, k may be 0) every crossing within tmax.
+    // flags = BM_MULTI_COUNT_ALL (deviceCounts required, k may be 0) every crossing within tmax. The filter bits
+    // of traceRays combine with it.
     u32 traceRaysMulti(const bm_ray* deviceRays, u32 n, u32 k, bm_hit* deviceHits, uint32_t* deviceCounts = nullptr,
                        u32 flags = 0) {
         return (u32)bm_scene_trace_rays_multi(h_, deviceRays, n, k, flags, deviceHits, deviceCounts);
@@ -300,6 +302,10 @@ class IScene {
         return (u32)bm_scene_get_instance_transform(h_, index, xformOut);
     }
     u32 removeInstance(u32 index) { return (u32)bm_scene_remove_instance(h_, index); }
+    // Extension: the 32-bit visibility mask of the entry at index, plain or instance (default 0xFFFFFFFF), which
+    // BM_RAYS_PAD_MASK ray queries test against each ray's mask; no rebuild needed (bm_scene_set_entry_mask).
+    u32 setEntryMask(u32 index, u32 mask) { return (u32)bm_scene_set_entry_mask(h_, index, mask); }
+    u32 getEntryMask(u32 index, u32* maskOut) const { return (u32)bm_scene_get_entry_mask(h_, index, maskOut); }
     bm_scene* handle() const { return h_; }
 
    private:

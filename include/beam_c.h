@@ -304,12 +304,54 @@ void bm_scene_destroy(bm_scene* s);
  *   this mode.
  * Invalid rays (a non-finite origin or direction component; closest mode: tmax NaN or <= 0) are not
  * traced: they get the miss record, or 0.
- * flags: none defined yet, pass 0. Rays are traced in the order given, 16 consecutive rays per
- *   wave: neighbours that start and point alike share their node fetches.
+ * flags: 0, or the filter bits below (BM_RAYS_CULL_*, BM_RAYS_PAD_*); with flags = 0 pad is ignored.
+ *   Rays are traced in the order given, 16 consecutive rays per wave: neighbours that start and
+ *   point alike share their node fetches.
  * BM_ERROR_INVALID_PARAMETER: a null handle, a null pointer with n > 0, a misaligned pointer, an
- * unknown mode or flag bit, a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT:
- * the scene has no current build. n = 0 succeeds without a launch; over an empty built scene every
- * ray misses. */
+ * unknown mode or flag bit, both cull flags or more than one BM_RAYS_PAD_* flag, a scene of a
+ * reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT: the scene has no current build. n = 0
+ * succeeds without a launch; over an empty built scene every ray misses.
+ *
+ * Filters (flags of bm_scene_trace_rays, bm_scene_trace_rays_multi and their counting forms; in the
+ * multi-hit calls they combine freely with BM_MULTI_COUNT_ALL). The set of triangles a ray accepts
+ * is the unfiltered one (0 < t <= tmax, any hit: 0 < t < 1, multi-hit: H_i below) intersected with
+ * the filter: a pure function of the call's flags, the ray's pad word, the candidate's global
+ * triangle id g, its det and t of the triangle function (stated at the multi-hit queries below) and
+ * the mask of the scene entry that owns g.
+ *   BM_RAYS_CULL_BACK      accept only det > 0. det = dot(e1, cross(d, e2)) is the triangle function's
+ *                          own; det > 0 <=> the ray runs against cross(e1, e2), the BM_ATTR_GEOM_NORMAL
+ *                          direction: a front-facing hit.
+ *   BM_RAYS_CULL_FRONT     accept only det < 0.
+ *   BM_RAYS_PAD_SKIP_TRI   pad is a global triangle id that is never accepted (the triangle a
+ *                          secondary ray starts on: the exact cure for self-intersection).
+ *                          BM_NO_TRIANGLE, or an id >= the built triangle count, skips nothing.
+ *   BM_RAYS_PAD_TMIN       pad holds the bits of a float tmin: accept t > tmin in place of t > 0 (any
+ *                          hit: tmin < t < 1). tmin must be finite and >= 0; a NaN, negative or
+ *                          infinite tmin makes the ray invalid (the miss record or 0, not traced).
+ *                          tmin >= tmax is valid and misses.
+ *   BM_RAYS_PAD_MASK       pad is a 32-bit ray mask: accept when (entry_mask[m(g)] & pad) != 0, m(g)
+ *                          the scene entry that owns g (bm_scene_set_entry_mask). pad = 0 is valid and
+ *                          misses everything.
+ * A triangle the triangle function accepts never has det == 0 (its u is then +-inf or NaN and its t
+ *   NaN), so front and back partition the unfiltered accepted set. Instances: facing is that of the
+ *   world-space triangle, so a mirroring matrix flips it exactly as it flips BM_ATTR_GEOM_NORMAL.
+ * Equal t resolves to the lowest id among the triangles the filter accepts: with a mesh added twice
+ *   on one spot, skipping g returns its twin at the same t. A rejected triangle never tightens the
+ *   traversal's bound (the closest t, the multi-hit list and its last t); the box test is the
+ *   unfiltered one, conservative for any tmin >= 0. Results equal a brute force over all triangles
+ *   bit for bit.
+ * Counters of filtered calls: out[0] and out[1] as without a filter (node records fetched, a leaf's
+ *   triangle count per leaf reached; any hit: the tests up to the first accepted occluder), out[2]
+ *   counts hits after the filter. A filter that can reject nothing (BM_RAYS_PAD_SKIP_TRI with pad =
+ *   BM_NO_TRIANGLE, BM_RAYS_PAD_TMIN with pad = 0.0f, BM_RAYS_PAD_MASK with pad = 0xFFFFFFFF over
+ *   default masks) gives the results and all counters of flags = 0, bit for bit.
+ * BM_RAYS_CULL_BACK | BM_RAYS_CULL_FRONT together, or more than one BM_RAYS_PAD_* flag (one call
+ *   gives pad one meaning), is BM_ERROR_INVALID_PARAMETER. */
+#define BM_RAYS_CULL_BACK 0x10u
+#define BM_RAYS_CULL_FRONT 0x20u
+#define BM_RAYS_PAD_SKIP_TRI 0x40u
+#define BM_RAYS_PAD_TMIN 0x80u
+#define BM_RAYS_PAD_MASK 0x100u
 typedef struct bm_ray {
     float origin[3];
     float tmax;
@@ -329,6 +371,18 @@ int32_t bm_scene_trace_rays(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uin
  * exactly as bm_scene_trace_rays writes them. Synchronous. */
 int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode,
                                      uint32_t flags, void* out_dev, uint64_t out[3]);
+
+/* Entry masks: one 32-bit visibility mask per scene entry (index: the entry index of the instance
+ * section below, plain and instance entries alike), read by BM_RAYS_PAD_MASK queries only — camera
+ * traces, shadow traces, point queries and unflagged ray queries never read them. Every new entry
+ * has 0xFFFFFFFF. The mask belongs to its entry: it survives bm_scene_build and bm_scene_refit, moves
+ * down with its entry when an earlier one is removed, and dies with it. Setting a mask launches
+ * nothing and does not unbuild the scene; it applies to queries enqueued after the call (earlier
+ * ones keep the old value, by stream order). The owner of a triangle is found from the entries'
+ * triangle counts of the last build.
+ * BM_ERROR_INVALID_PARAMETER: a null handle, an index past the entries, a null mask_out. */
+int32_t bm_scene_set_entry_mask(bm_scene* s, uint32_t index, uint32_t mask);
+int32_t bm_scene_get_entry_mask(const bm_scene* s, uint32_t index, uint32_t* mask_out);
 
 /* ---- multi-hit ray queries: the k nearest hits of each ray, and hit counts --------------------
  * What lies behind the first surface: the first k layers along a ray in order (transparency, X-ray
@@ -373,7 +427,8 @@ int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32
  * bit; a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT: the scene has no
  * current build. n = 0 succeeds without a launch. */
 #define BM_MULTI_MAX_HITS 16u
-#define BM_MULTI_COUNT_ALL 1u /* flags */
+#define BM_MULTI_COUNT_ALL 1u /* flags; the filter bits BM_RAYS_CULL_* / BM_RAYS_PAD_* above combine with it: H_i
+                               * is then the filtered set, and an invalid tmin (BM_RAYS_PAD_TMIN) an invalid ray */
 int32_t bm_scene_trace_rays_multi(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t k,
                                   uint32_t flags, bm_hit* hits_dev, uint32_t* counts_dev);
 /* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle tests (a

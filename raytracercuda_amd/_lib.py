@@ -93,6 +93,10 @@ class Hit(C.Structure):
 RAYS_CLOSEST, RAYS_ANY_HIT = 0, 1
 MULTI_MAX_HITS = 16   # BM_MULTI_MAX_HITS: records per ray of bm_scene_trace_rays_multi (per point of
                       # bm_scene_closest_points_multi)
+# filter flags of the ray queries (bm_scene_trace_rays, bm_scene_trace_rays_multi): face culling, and what the
+# ray's pad word means — a global triangle id to skip, the bits of a float tmin, or a ray mask against the
+# scene entries' masks
+RAYS_CULL_BACK, RAYS_CULL_FRONT, RAYS_PAD_SKIP_TRI, RAYS_PAD_TMIN, RAYS_PAD_MASK = 0x10, 0x20, 0x40, 0x80, 0x100
 MULTI_COUNT_ALL = 1   # their flag: count every crossing within tmax (every triangle within rmax)
 
 
@@ -156,6 +160,8 @@ SIGNATURES = {
     "bm_scene_set_instance_transform": (_I, [_P, _U, _FP]),
     "bm_scene_get_instance_transform": (_I, [_P, _U, _FP]),
     "bm_scene_remove_instance": (_I, [_P, _U]),
+    "bm_scene_set_entry_mask": (_I, [_P, _U, _U]),
+    "bm_scene_get_entry_mask": (_I, [_P, _U, _UP]),
     "bm_xform_normal_matrix": (_I, [_FP, _FP]),
     "bm_model_add_instance": (_I, [_P, _P, _P, _FP]),
     "bm_scene_build": (_I, [_P, C.POINTER(BuildStats)]),

@@ -44,6 +44,55 @@ def _up(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
+def ray_filter_flags(cull=None, skip_tri=None, tmin=None, ray_mask=None) -> int:
+    """The filter flag bits of a ray query: cull None, "back" or "front", and at most one meaning for the
+    rays' pad word — skip_tri (a global triangle id never accepted), tmin (accept t > tmin) or ray_mask
+    (accept entries whose mask shares a bit with it)."""
+    culls = {None: 0, "back": _lib.RAYS_CULL_BACK, "front": _lib.RAYS_CULL_FRONT}
+    if cull not in culls:
+        raise BeamError(ERROR_INVALID_PARAMETER, 'cull: None, "back" or "front"')
+    given = [f for v, f in ((skip_tri, _lib.RAYS_PAD_SKIP_TRI), (tmin, _lib.RAYS_PAD_TMIN),
+                            (ray_mask, _lib.RAYS_PAD_MASK)) if v is not None]
+    if len(given) > 1:
+        raise BeamError(ERROR_INVALID_PARAMETER, "at most one of skip_tri, tmin and ray_mask: the pad word has one meaning")
+    return culls[cull] | (given[0] if given else 0)
+
+
+def ray_pad_words(n: int, skip_tri=None, tmin=None, ray_mask=None):
+    """The pad column of n bm_ray records as uint32 for one of skip_tri (ids; -1 is NO_TRIANGLE), tmin (float32
+    bits) and ray_mask, each a scalar or n values; None when none is given."""
+    if tmin is not None:
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, np.float32), (n,))).view(np.uint32)
+    v = skip_tri if skip_tri is not None else ray_mask
+    if v is None:
+        return None
+    a = np.asarray(v)
+    if a.dtype.kind not in "iu":
+        raise BeamError(ERROR_INVALID_PARAMETER, "skip_tri and ray_mask are integers")
+    return np.ascontiguousarray(np.broadcast_to((a.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32), (n,)))
+
+
+def _write_pad(rays, skip_tri=None, tmin=None, ray_mask=None) -> None:
+    """Write the pad column of a packed (n,8) float32 torch tensor from torch tensors or host values, on the
+    device and with the right bit pattern."""
+    import torch
+    n = rays.shape[0]
+    col = rays.view(torch.int32)[:, 7]
+    v = tmin if tmin is not None else skip_tri if skip_tri is not None else ray_mask
+    if v is None:
+        return
+    if isinstance(v, torch.Tensor):
+        if tmin is not None:
+            rays[:, 7] = v.to(torch.float32)
+        elif v.dtype == torch.int32:
+            col[:] = v
+        else:  # wider integers: the low 32 bits
+            col[:] = (((v.to(torch.int64) & 0xFFFFFFFF) + 2 ** 31) % 2 ** 32 - 2 ** 31).to(torch.int32)
+    else:
+        words = ray_pad_words(n, skip_tri, tmin, ray_mask)
+        col[:] = torch.from_numpy(words.view(np.int32).copy()).to(rays.device)
+
+
 def _xform12(xform) -> np.ndarray:
     """An instance transform as 12 contiguous float32, row-major 3x4: from 12 floats, a (3,4) array, or a
     (4,4) array whose last row is exactly [0,0,0,1]. Anything else is a ValueError."""
@@ -289,6 +338,16 @@ class IScene:
         """Erase the entry at index (plain or instance); later entries move down by one."""
         self.ctx._check(self.ctx.lib.bm_scene_remove_instance(self.h, index))
 
+    def setEntryMask(self, index: int, mask: int) -> None:
+        """bm_scene_set_entry_mask: the 32-bit visibility mask of the entry at index, plain or instance (default
+        0xFFFFFFFF). No rebuild: ray queries with ray_mask= enqueued after the call see it."""
+        self.ctx._check(self.ctx.lib.bm_scene_set_entry_mask(self.h, index, mask & 0xFFFFFFFF))
+
+    def getEntryMask(self, index: int) -> int:
+        out = C.c_uint32(0)
+        self.ctx._check(self.ctx.lib.bm_scene_get_entry_mask(self.h, index, C.byref(out)))
+        return int(out.value)
+
     def updateGPUScene(self, stats: bool = False):
         """Rebuild the BVH from the current meshes (asynchronous unless stats=True)."""
         st = BuildStats()
@@ -351,7 +410,7 @@ class IScene:
         """bm_scene_trace_rays on device pointers (n bm_ray records of 32 bytes in, n bm_hit records of
         16 bytes or n bytes out, both 16-byte aligned); returns the error code. Asynchronous on the
         context stream unless `counters` (a uint64[3] numpy array to fill) is given. mode overrides
-        any_hit with a raw value; flags: none defined yet."""
+        any_hit with a raw value; flags: 0 or filter bits (RAYS_CULL_*, RAYS_PAD_*: the records' pad words)."""
         mode = (_lib.RAYS_ANY_HIT if any_hit else _lib.RAYS_CLOSEST) if mode is None else mode
         rp, op = C.c_void_p(rays_ptr or None), C.c_void_p(out_ptr or None)
         if counters is None:
@@ -359,7 +418,8 @@ class IScene:
         return self.ctx.lib.bm_scene_trace_rays_counters(self.h, rp, n, mode, flags, op,
                                                          counters.ctypes.data_as(C.POINTER(C.c_uint64)))
 
-    def traceRays(self, origins, dirs=None, tmax=None, any_hit: bool = False, counters: bool = False):
+    def traceRays(self, origins, dirs=None, tmax=None, any_hit: bool = False, counters: bool = False, cull=None,
+                  skip_tri=None, tmin=None, ray_mask=None, flags: int = 0):
         """Closest hit (or, any_hit, occlusion of the segment origin -> origin + dir) of n rays of the
         caller's own (bm_scene_trace_rays). tmax: None (unbounded), a scalar or n values; closest mode only.
 
@@ -371,10 +431,23 @@ class IScene:
         last column as int32, -1 on a miss) or {"occluded": (n,) uint8}. Make the context on torch's
         stream (Context(stream=torch.cuda.current_stream().cuda_stream)) so the query is ordered with
         the torch work around it.
+        Filters: cull="back" / "front" accepts front-facing (back-facing) hits only; one of skip_tri (a global
+        triangle id the ray never hits, e.g. the tri_id it starts on; -1 skips nothing), tmin (accept
+        t > tmin, finite and >= 0) and ray_mask (accept entries whose setEntryMask mask shares a bit with it),
+        each a scalar or n values (numpy, or torch on the device), goes into the rays' pad words. The packed
+        (n,8) form carries its own pad column: pass the bits as flags= (RAYS_CULL_*, RAYS_PAD_*).
         counters=True adds "counters": [node records, triangle tests, hits or occluded rays] (waits)."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
         on_device = isinstance(origins, torch.Tensor)
+        packed_in = on_device and dirs is None
+        if packed_in:
+            if cull is not None or skip_tri is not None or tmin is not None or ray_mask is not None:
+                raise BeamError(ERROR_INVALID_PARAMETER, "traceRays: packed rays carry their pad column; pass flags=")
+        else:
+            if flags:
+                raise BeamError(ERROR_INVALID_PARAMETER, "traceRays: flags= goes with packed (n, 8) rays")
+            flags = ray_filter_flags(cull, skip_tri, tmin, ray_mask)
         if on_device:
             if dirs is None:
                 rays = origins
@@ -386,6 +459,7 @@ class IScene:
                 rays[:, 0:3] = origins
                 rays[:, 3] = float("inf") if tmax is None else tmax
                 rays[:, 4:7] = dirs
+                _write_pad(rays, skip_tri, tmin, ray_mask)
             if rays.device != dev or rays.dtype != torch.float32 or not rays.is_contiguous():
                 raise BeamError(ERROR_INVALID_PARAMETER,
                                 f"traceRays: rays must be contiguous float32 on {dev} (the context's device)")
@@ -395,6 +469,9 @@ class IScene:
             packed[:, 0:3] = o
             packed[:, 3] = np.inf if tmax is None else tmax
             packed[:, 4:7] = _f32(dirs).reshape(-1, 3)
+            pad = ray_pad_words(o.shape[0], skip_tri, tmin, ray_mask)
+            if pad is not None:
+                packed.view(np.uint32)[:, 7] = pad
             rays = torch.from_numpy(packed).to(dev)
             torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
         n = rays.shape[0]
@@ -402,7 +479,7 @@ class IScene:
                else torch.empty((n, 4), dtype=torch.float32, device=dev))
         cnt = np.zeros(3, np.uint64) if counters else None
         self.ctx._check(self.traceRaysDevice(rays.data_ptr() if n else 0, n, out.data_ptr() if n else 0, any_hit,
-                                             cnt))
+                                             cnt, flags=flags))
         self._rays_keep = rays  # until the next query: the kernel may not have read them yet
         if on_device:
             res = ({"occluded": out} if any_hit else
@@ -422,7 +499,7 @@ class IScene:
         """bm_scene_trace_rays_multi on device pointers (n bm_ray records of 32 bytes in, n * k bm_hit records
         of 16 bytes out, both 16-byte aligned; counts_ptr: n uint32, or 0); returns the error code.
         Asynchronous on the context stream unless `counters` (a uint64[3] numpy array to fill) is given.
-        flags: MULTI_COUNT_ALL or 0."""
+        flags: MULTI_COUNT_ALL and the filter bits of traceRaysDevice, or 0."""
         rp, hp, cp = C.c_void_p(rays_ptr or None), C.c_void_p(hits_ptr or None), C.c_void_p(counts_ptr or None)
         if counters is None:
             return self.ctx.lib.bm_scene_trace_rays_multi(self.h, rp, n, k, flags, hp, cp)
@@ -430,7 +507,7 @@ class IScene:
                                                                counters.ctypes.data_as(C.POINTER(C.c_uint64)))
 
     def traceRaysMulti(self, origins, dirs=None, tmax=None, k: int = 4, count_all: bool = False,
-                       counters: bool = False):
+                       counters: bool = False, cull=None, skip_tri=None, tmin=None, ray_mask=None, flags: int = 0):
         """The k nearest hits of each of n rays in (t, id) order (bm_scene_trace_rays_multi), k = 1..16, and
         per ray "count": the records that are hits, or with count_all every crossing within tmax (k may then
         be 0). Rays and tmax as for traceRays.
@@ -440,10 +517,18 @@ class IScene:
         torch tensors on the context's device: nothing waits. Returns {"hits": (n, k, 4) float32, "t", "u", "v",
         "tri_id" (views of hits, (n, k); tri_id as int32, -1 in a miss slot), "count": (n,) int32};
         res["hits"].view(-1, 4) goes straight into hitAttributes as n * k hits.
+        Filters (cull, skip_tri, tmin, ray_mask; flags= with packed rays, beside count_all) as for traceRays.
         counters=True adds "counters": [node records, triangle tests, the sum of the counts] (waits)."""
         import torch
         dev = torch.device("cuda", self.ctx.device)
         on_device = isinstance(origins, torch.Tensor)
+        if on_device and dirs is None:
+            if cull is not None or skip_tri is not None or tmin is not None or ray_mask is not None:
+                raise BeamError(ERROR_INVALID_PARAMETER, "traceRaysMulti: packed rays carry their pad column; pass flags=")
+        else:
+            if flags:
+                raise BeamError(ERROR_INVALID_PARAMETER, "traceRaysMulti: flags= goes with packed (n, 8) rays")
+            flags = ray_filter_flags(cull, skip_tri, tmin, ray_mask)
         if on_device:
             if dirs is None:
                 rays = origins
@@ -454,6 +539,7 @@ class IScene:
                 rays[:, 0:3] = origins
                 rays[:, 3] = float("inf") if tmax is None else tmax
                 rays[:, 4:7] = dirs
+                _write_pad(rays, skip_tri, tmin, ray_mask)
             if rays.device != dev or rays.dtype != torch.float32 or not rays.is_contiguous():
                 raise BeamError(ERROR_INVALID_PARAMETER,
                                 f"traceRaysMulti: rays must be contiguous float32 on {dev} (the context's device)")
@@ -463,6 +549,9 @@ class IScene:
             packed[:, 0:3] = o
             packed[:, 3] = np.inf if tmax is None else tmax
             packed[:, 4:7] = _f32(dirs).reshape(-1, 3)
+            pad = ray_pad_words(o.shape[0], skip_tri, tmin, ray_mask)
+            if pad is not None:
+                packed.view(np.uint32)[:, 7] = pad
             rays = torch.from_numpy(packed).to(dev)
             torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
         n = rays.shape[0]
@@ -471,7 +560,7 @@ class IScene:
         cnt = np.zeros(3, np.uint64) if counters else None
         self.ctx._check(self.traceRaysMultiDevice(rays.data_ptr() if n else 0, n, k, out.data_ptr() if n and k else 0,
                                                   count.data_ptr() if n else 0,
-                                                  _lib.MULTI_COUNT_ALL if count_all else 0, cnt))
+                                                  (_lib.MULTI_COUNT_ALL if count_all else 0) | flags, cnt))
         self._rays_keep = rays  # until the next query: the kernel may not have read them yet
         if on_device:
             res = {"hits": out, "t": out[..., 0], "u": out[..., 1], "v": out[..., 2],

@@ -141,6 +141,7 @@ struct bm_scene {
     struct Entry {
         bool inst = false;      // made by bm_scene_add_instance
         float x[12] = {};       // its transform, row-major 3x4
+        uint32_t mask = 0xFFFFFFFFu;  // bm_scene_set_entry_mask: read by BM_RAYS_PAD_MASK ray queries only
         uint32_t built_nv = 0;  // the last build or refit filled the pools for this many vertices at pool_off
         size_t pool_off = 0;    // floats from the start of inst_pos / inst_nrm (a multiple of 4)
     };
@@ -198,6 +199,14 @@ struct bm_scene {
     unsigned char* attr_staging = nullptr;
     size_t attr_staging_cap = 0;
     hipEvent_t attr_done = nullptr;    // the last upload has left attr_staging
+    // entry masks (BM_RAYS_PAD_MASK ray queries): for the entries that own triangles in the last build, their
+    // first global ids and then their masks; uploaded like attr_table, when a masked query finds it differs
+    // from mask_host
+    DevBuf mask_table;
+    std::vector<uint32_t> mask_host;
+    uint32_t* mask_staging = nullptr;
+    size_t mask_staging_cap = 0;
+    hipEvent_t mask_done = nullptr;    // the last upload has left mask_staging
 };
 
 struct bm_camera {
@@ -838,6 +847,22 @@ int32_t bm_scene_remove_instance(bm_scene* s, uint32_t index) {
     if (!s) return BM_ERROR_INVALID_PARAMETER;
     if (index >= s->entries.size()) return fail(s->ctx, BM_ERROR_INVALID_PARAMETER, "removeInstance: no such entry");
     scene_erase_entry(s, index);
+    return BM_ERROR_ALL_FINE;
+}
+
+// ---- entry masks (BM_RAYS_PAD_MASK ray queries) ---------------------------------------------------
+// Host state only: the next masked query uploads the table if it changed (filter_setup). Queries run on the
+// root device alone, so the replicas keep no masks.
+int32_t bm_scene_set_entry_mask(bm_scene* s, uint32_t index, uint32_t mask) {
+    if (!s) return BM_ERROR_INVALID_PARAMETER;
+    if (index >= s->entries.size()) return fail(s->ctx, BM_ERROR_INVALID_PARAMETER, "setEntryMask: no such entry");
+    s->entries[index].mask = mask;
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_get_entry_mask(const bm_scene* s, uint32_t index, uint32_t* mask_out) {
+    if (!s || !mask_out || index >= s->entries.size()) return BM_ERROR_INVALID_PARAMETER;
+    *mask_out = s->entries[index].mask;
     return BM_ERROR_ALL_FINE;
 }
 
@@ -1516,12 +1541,14 @@ void bm_scene_destroy(bm_scene* s) {
                       &s->kd_lch, &s->kd_rch, &s->kd_first, &s->kd_last, &s->kd_pleaf, &s->kd_pint, &s->kd_nodes, &s->kd_cnodes,
                       &s->kd_leafrec, &s->kd_ftris, &s->kd_node_key, &s->kd_ubox, &s->kd_cache,
                       &s->kd_queue, &s->kd_fill, &s->hash_bstart, &s->hash_bend, &s->attr_table, &s->inst_pos,
-                      &s->inst_nrm, &s->inst_table})
+                      &s->inst_nrm, &s->inst_table, &s->mask_table})
         b->release();
     if (s->inst_staging) (void)hipHostFree(s->inst_staging);
     if (s->inst_done) (void)hipEventDestroy(s->inst_done);
     if (s->attr_staging) (void)hipHostFree(s->attr_staging);
     if (s->attr_done) (void)hipEventDestroy(s->attr_done);
+    if (s->mask_staging) (void)hipHostFree(s->mask_staging);
+    if (s->mask_done) (void)hipEventDestroy(s->mask_done);
     if (s->staging) (void)hipHostFree(s->staging);
     if (s->hbounds) (void)hipHostFree(s->hbounds);
     if (s->kd_post) (void)hipHostFree(s->kd_post);
@@ -1921,6 +1948,62 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
 // One path for both: the checks in the order beam_c.h lists them, the quad kernels' launch parameters on the
 // context stream with the overflow area reserved, the launch, and for the counting forms the counters read
 // back (3 words for rays, 4 for points; synchronous). points: a closest-point query (mode is not read).
+// The filter bits of a ray query (beam_c.h): known bits only, one cull flag, one meaning for pad.
+static bool filter_flags_valid(uint32_t f) {
+    constexpr uint32_t pad_bits = BM_RAYS_PAD_SKIP_TRI | BM_RAYS_PAD_TMIN | BM_RAYS_PAD_MASK;
+    if (f & ~(BM_RAYS_CULL_BACK | BM_RAYS_CULL_FRONT | pad_bits)) return false;
+    if ((f & BM_RAYS_CULL_BACK) && (f & BM_RAYS_CULL_FRONT)) return false;
+    const uint32_t pad = f & pad_bits;
+    return (pad & (pad - 1u)) == 0;
+}
+
+// The filter's launch parameters for a built BVH4 scene. BM_RAYS_PAD_MASK: the owner table — the entries
+// that own triangles in the last build (built_with's counts; an entry without triangles owns none), their
+// first global ids and then their masks — goes up on the context stream when it differs from the last
+// image uploaded, so a mask set between two queries applies to the second alone, by stream order.
+static int32_t filter_setup(bm_scene* s, uint32_t flags, hipStream_t st, bm::TraceParams& p) {
+    bm_context* ctx = s->ctx;
+    p.q_flags = flags;
+    if (!(flags & BM_RAYS_PAD_MASK)) return BM_ERROR_ALL_FINE;
+    if (s->built_with.size() != s->entries.size())
+        return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
+    std::vector<uint32_t> first, mask;
+    uint32_t off = 0;
+    for (size_t i = 0; i < s->entries.size(); ++i) {
+        if (s->built_with[i].second) {
+            first.push_back(off);
+            mask.push_back(s->entries[i].mask);
+        }
+        off += s->built_with[i].second;
+    }
+    if (off != s->n) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
+    const size_t ne = first.size();
+    std::vector<uint32_t> image(first);
+    image.insert(image.end(), mask.begin(), mask.end());
+    if (ne && image != s->mask_host) {
+        const size_t bytes = image.size() * sizeof(uint32_t);
+        s->mask_host.clear();  // unknown until the new image is on its way
+        if (!s->mask_done) BM_HIP(ctx, hipEventCreateWithFlags(&s->mask_done, hipEventDisableTiming));
+        else BM_HIP(ctx, hipEventSynchronize(s->mask_done));  // the previous upload still reads the staging area
+        if (bytes > s->mask_staging_cap) {
+            if (s->mask_staging) (void)hipHostFree(s->mask_staging);
+            s->mask_staging = nullptr;
+            s->mask_staging_cap = 0;
+            BM_HIP(ctx, hipHostMalloc((void**)&s->mask_staging, bytes, hipHostMallocDefault));
+            s->mask_staging_cap = bytes;
+        }
+        GrowGuard grow{ctx};  // an earlier query still queued may read the old table
+        BM_HIP(ctx, grow.reserve(s->mask_table, bytes));
+        std::memcpy(s->mask_staging, image.data(), bytes);
+        BM_HIP(ctx, hipMemcpyAsync(s->mask_table.p, s->mask_staging, bytes, hipMemcpyHostToDevice, st));
+        BM_HIP(ctx, hipEventRecord(s->mask_done, st));
+        s->mask_host = std::move(image);
+    }
+    p.q_ent_n = (uint32_t)ne;
+    p.q_ent = ne ? s->mask_table.as<const uint32_t>() : nullptr;
+    return BM_ERROR_ALL_FINE;
+}
+
 static int32_t query_impl(bm_scene* s, bool points, const void* in, uint32_t n, uint32_t mode, uint32_t flags,
                           void* out, uint64_t* counters) {
     if (!s) return BM_ERROR_INVALID_PARAMETER;
@@ -1929,7 +2012,7 @@ static int32_t query_impl(bm_scene* s, bool points, const void* in, uint32_t n, 
     if (n && (!in || !out)) return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "null input or result pointer");
     if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "input and result pointers must be 16-byte aligned");
-    if ((!points && mode > BM_RAYS_ANY_HIT) || flags != 0)  // no flag bits are defined
+    if ((!points && mode > BM_RAYS_ANY_HIT) || (points ? flags != 0 : !filter_flags_valid(flags)))  // points: no flag bits
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "unknown mode or flag bits");
     if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
@@ -1952,6 +2035,8 @@ static int32_t query_impl(bm_scene* s, bool points, const void* in, uint32_t n, 
     p.q_rays = reinterpret_cast<const float4*>(in);
     p.q_out = out;
     p.q_n = n;
+    if (!points)
+        if (const int32_t e = filter_setup(s, flags, st, p)) return e;
     if (const int32_t e = reserve_overflow(ctx, nullptr, st, p)) return e;
     if (counters) {
         if (!ctx->rays_counters) BM_HIP(ctx, hipMalloc(&ctx->rays_counters, 4 * sizeof(unsigned long long)));
@@ -2007,7 +2092,8 @@ static int32_t multi_impl(bm_scene* s, bool points, const void* rays, uint32_t n
         (reinterpret_cast<uintptr_t>(counts) & 3u))
         return fail(ctx, BM_ERROR_INVALID_PARAMETER,
                     who + what + " and hit pointers must be 16-byte aligned, the count pointer 4-byte");
-    if ((flags & ~BM_MULTI_COUNT_ALL) || k > BM_MULTI_MAX_HITS || (k == 0 && !all))
+    const uint32_t filter = flags & ~BM_MULTI_COUNT_ALL;  // rays: the filter bits; points have none
+    if ((points ? filter != 0 : !filter_flags_valid(filter)) || k > BM_MULTI_MAX_HITS || (k == 0 && !all))
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "k out of range or unknown flag bits");
     if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
@@ -2032,6 +2118,8 @@ static int32_t multi_impl(bm_scene* s, bool points, const void* rays, uint32_t n
     p.q_n = n;
     p.q_k = k;
     p.q_counts = counts;
+    if (!points)
+        if (const int32_t e = filter_setup(s, filter, st, p)) return e;
     if (const int32_t e = reserve_overflow(ctx, nullptr, st, p)) return e;
     if (counters) {
         if (!ctx->rays_counters) BM_HIP(ctx, hipMalloc(&ctx->rays_counters, 4 * sizeof(unsigned long long)));

@@ -115,6 +115,17 @@ __device__ __forceinline__ bool tri_test(const float4 a, const float4 b, const f
     return in;
 }
 
+// tri_test's determinant alone, by its own statements on the same operands (bit-identical to the det it
+// divides by): positive when the ray runs against cross(e1, e2) — a front-facing hit — negative when along
+// it. A triangle tri_test accepts with a t that compares never has det == 0: its u would be +-inf or NaN and
+// its t NaN. For the ray query filters (bm_trace_quad.h filter_accept), which need it only for a triangle
+// already accepted: recomputed there, it costs the triangle test's registers nothing.
+__device__ __forceinline__ float tri_det(const float4 b, const float4 c, const vec3f dir) {
+    const vec3f e1 = v3(b.x, b.y, b.z), e2 = v3(c.x, c.y, c.z);
+    const vec3f pv = cross(dir, e2);
+    return dot(e1, pv);
+}
+
 // Wave64 ballot of a bool: the compare mask itself. HIP's __ballot takes an int predicate, so a bool
 // argument costs a select to 0/1 and a compare back per call (BM_BOOL_BALLOT 0 restores it for A/B).
 #ifndef BM_BOOL_BALLOT

@@ -196,6 +196,12 @@ struct TraceParams {
     // the same two per point
     uint32_t q_k;
     uint32_t* q_counts;
+    // ray query filters (bm_trace_quad.h RayFilter): the call's BM_RAYS_* filter bits (0: the unfiltered
+    // kernels) and, for BM_RAYS_PAD_MASK, the owner table of the last build: q_ent_n entries that own
+    // triangles, q_ent[i] the first global id of entry i (ascending), q_ent[q_ent_n + i] its mask
+    uint32_t q_flags;
+    uint32_t q_ent_n;
+    const uint32_t* q_ent;
 };
 
 bool trace_variant_persistent(int variant);

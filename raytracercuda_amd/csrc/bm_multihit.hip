@@ -23,10 +23,14 @@ namespace {
 // The k nearest hits of one ray over the quad, and with ALL the number of accepted triangles. One
 // iteration is quad_closest's: the pending leaf, the pop that follows it, the node visit(s).
 // cnt: entries in the list on return; total (ALL): |H|, the same in every lane of the quad.
-template <bool COUNT, uint32_t PRIO, bool ALL, int CAP, typename QS>
+// FILTER (calls with filter flags; fray: the ray's index in the batch): a triangle accepted within the bound — the
+// list's for a pruned query, tmax when everything is counted — is also put to filter_accept
+// (bm_trace_quad.h); a rejected one is no candidate and is not counted. Off, the code is the unfiltered one.
+template <bool COUNT, uint32_t PRIO, bool ALL, int CAP, bool FILTER, typename QS>
 __device__ __forceinline__ void quad_multi(const TraceParams& p, const QS& st, const HitList<CAP>& hl, int c, uint32_t k,
                                            const vec3f o, const vec3f dir, const vec3f inv, float tmax, uint32_t& cnt,
-                                           uint32_t& total, unsigned long long& cn, unsigned long long& ct) {
+                                           uint32_t& total, unsigned long long& cn, unsigned long long& ct,
+                                           uint32_t fray = 0) {
     int sp = 0;
     uint32_t next = p.num_tris ? 0u : EMPTY_REF;
     if (COUNT && !p.num_tris && c == 0) ++cn;  // an empty scene: the all-empty root record, as quad_closest counts it
@@ -44,7 +48,11 @@ __device__ __forceinline__ void quad_multi(const TraceParams& p, const QS& st, c
                 if (k0 + c < lcnt) {
                     const float4 a = p.tris[3 * ti + 0], b = p.tris[3 * ti + 1], cc = p.tris[3 * ti + 2];
                     float tt, uu, vv;
-                    if (tri_test(a, b, cc, o, dir, tt, uu, vv) && tt > 0.0f && tt < 3.40282347e+38f && tt <= tmax) {
+                    bool acc = tri_test(a, b, cc, o, dir, tt, uu, vv) && tt > 0.0f && tt < 3.40282347e+38f && tt <= tmax;
+                    if constexpr (FILTER)
+                        acc = acc && (ALL || tt <= (cnt == k ? tlast : tmax)) &&
+                              filter_accept<true>(p, fray, ti, f2u(a.w), dir, tt);
+                    if (acc) {
                         t = tt;
                         id = f2u(a.w);
                         u = uu;
@@ -105,7 +113,8 @@ __device__ __forceinline__ void quad_multi(const TraceParams& p, const QS& st, c
 // Ray records as in k_query_rays; an invalid ray (closest mode's rule) is finished without traversal: k
 // miss records, count 0. Lane c stores records j = c, c + 4, ... of its ray's k contiguous records
 // straight from the list (16-B stores), the miss record beyond the list's end.
-template <bool COUNT, uint32_t PRIO, bool ALL, int CAP>
+// FILTER: as in k_query_rays.
+template <bool COUNT, uint32_t PRIO, bool ALL, int CAP, bool FILTER>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : CAP > MULTI_CAP_SMALL ? MULTI_WAVES_LARGE
                                                                                                        : QUAD_WAVES))) void
 k_query_multi(const TraceParams p) {
@@ -128,12 +137,13 @@ k_query_multi(const TraceParams p) {
         const float4 r0 = p.q_rays[2 * (size_t)sidx], r1 = p.q_rays[2 * (size_t)sidx + 1];
         const vec3f o = v3(r0.x, r0.y, r0.z), d = v3(r1.x, r1.y, r1.z);
         const float tmax = r0.w;
-        const bool valid = finite3(o) && finite3(d) && tmax > 0.0f;  // false for NaN
+        bool valid = finite3(o) && finite3(d) && tmax > 0.0f;  // false for NaN
+        if (FILTER && (p.q_flags & BM_RAYS_PAD_TMIN)) valid = valid && r1.w >= 0.0f && r1.w < __builtin_inff();
         __builtin_amdgcn_s_setprio(0);
         uint32_t cnt = 0, total = 0;
         if (valid) {
             const vec3f inv = v3(1.f / d.x, 1.f / d.y, 1.f / d.z);
-            quad_multi<COUNT, PRIO, ALL, CAP>(p, st, hl, c, k, o, d, inv, tmax, cnt, total, cn, ct);
+            quad_multi<COUNT, PRIO, ALL, CAP, FILTER>(p, st, hl, c, k, o, d, inv, tmax, cnt, total, cn, ct, sidx);
             if (COUNT && c == 0) ch += ALL ? total : cnt;
         }
         const size_t base = (size_t)sidx * k;
@@ -151,11 +161,17 @@ k_query_multi(const TraceParams p) {
     flush_counters<COUNT>(p, cn, ct, ch, none);
 }
 
+template <bool ALL, int CAP, bool FILTER>
+void launch_prio(const TraceParams& p, bool count, hipStream_t s) {
+    if (count) launch_persistent(k_query_multi<true, 1, ALL, CAP, FILTER>, p, s, nullptr);
+    else if (p.prio_after == 0) launch_persistent(k_query_multi<false, 0, ALL, CAP, FILTER>, p, s, nullptr);
+    else launch_persistent(k_query_multi<false, 1, ALL, CAP, FILTER>, p, s, nullptr);
+}
+
 template <bool ALL, int CAP>
 void launch_count(const TraceParams& p, bool count, hipStream_t s) {
-    if (count) launch_persistent(k_query_multi<true, 1, ALL, CAP>, p, s, nullptr);
-    else if (p.prio_after == 0) launch_persistent(k_query_multi<false, 0, ALL, CAP>, p, s, nullptr);
-    else launch_persistent(k_query_multi<false, 1, ALL, CAP>, p, s, nullptr);
+    if (p.q_flags) launch_prio<ALL, CAP, true>(p, count, s);
+    else launch_prio<ALL, CAP, false>(p, count, s);
 }
 
 }  // namespace
@@ -164,6 +180,7 @@ hipError_t launch_query_multi(const TraceParams& p, bool count_all, bool count, 
     if (p.q_n == 0) return hipSuccess;
     if (p.bvh_width != 4 || p.q_k > BM_MULTI_MAX_HITS || (p.q_k == 0 && !count_all) || (count_all && !p.q_counts))
         return hipErrorInvalidValue;
+    if ((p.q_flags & BM_RAYS_PAD_MASK) && p.q_ent_n && !p.q_ent) return hipErrorInvalidValue;
     const bool large = p.q_k > (uint32_t)MULTI_CAP_SMALL;
     if (count_all) {
         if (large) launch_count<true, MULTI_CAP_LARGE>(p, count, s);

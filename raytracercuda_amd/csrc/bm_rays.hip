@@ -22,8 +22,10 @@ __device__ __forceinline__ bool finite3(const vec3f a) {
 // A ray record is two float4: (origin, tmax) (dir, pad). The four lanes of a quad load the same 32
 // bytes (one request per 16-B piece). An invalid ray (a non-finite origin or direction component;
 // closest mode: tmax NaN or <= 0) is finished here without traversal, so no NaN reaches a traversal
-// loop: the miss record, or 0.
-template <int MODE, bool COUNT, uint32_t PRIO>
+// loop: the miss record, or 0. FILTER: the call has filter flags (p.q_flags); the traversal's filter reads the
+// ray's pad word, and with BM_RAYS_PAD_TMIN a pad that is not a finite float >= 0 makes the ray
+// invalid like the others.
+template <int MODE, bool COUNT, uint32_t PRIO, bool FILTER>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : QUAD_WAVES))) void
 k_query_rays(const TraceParams p) {
     __shared__ uint2 s_stk[QUAD_LDS][QRAYS];
@@ -40,6 +42,8 @@ k_query_rays(const TraceParams p) {
         const float4 r0 = p.q_rays[2 * (size_t)sidx], r1 = p.q_rays[2 * (size_t)sidx + 1];
         const vec3f o = v3(r0.x, r0.y, r0.z), d = v3(r1.x, r1.y, r1.z);
         bool valid = finite3(o) && finite3(d);
+        if (FILTER && (p.q_flags & BM_RAYS_PAD_TMIN))
+            valid = valid && r1.w >= 0.0f && r1.w < __builtin_inff();  // tmin: false for NaN
         __builtin_amdgcn_s_setprio(0);
         if (MODE == RAYS_CLOSEST) {
             const float tmax = r0.w;
@@ -49,7 +53,8 @@ k_query_rays(const TraceParams p) {
             if (valid) {
                 const vec3f inv = v3(1.f / d.x, 1.f / d.y, 1.f / d.z);
                 tbest = tmax;
-                quad_closest<COUNT, PRIO>(p, st, c, o, d, inv, tbest, ibest, bu, bv, cn, ct);
+                quad_closest<COUNT, PRIO, QStack<QUAD_LDS>, 4, FILTER>(p, st, c, o, d, inv, tbest, ibest, bu, bv, cn, ct,
+                                                                       sidx);
                 if (ibest == NO_TRI) tbest = __builtin_inff();
                 else if (COUNT && c == 0) ++ch;
             }
@@ -59,7 +64,7 @@ k_query_rays(const TraceParams p) {
         } else {
             bool occ = false;
             if (valid && p.num_tris) {  // quad_anyhit starts at the root without looking at num_tris
-                occ = quad_anyhit<COUNT, PRIO>(p, st, c, o, d, cn, ct);
+                occ = quad_anyhit<COUNT, PRIO, QStack<QUAD_LDS>, 4, FILTER>(p, st, c, o, d, cn, ct, sidx);
                 if (COUNT && c == 0) ch += occ;
             }
             if (c == 0) reinterpret_cast<uint8_t*>(p.q_out)[sidx] = occ ? 1 : 0;
@@ -68,11 +73,17 @@ k_query_rays(const TraceParams p) {
     flush_counters<COUNT>(p, cn, ct, ch, none);
 }
 
-template <int MODE>
+template <int MODE, bool FILTER>
 void launch_count(const TraceParams& p, bool count, hipStream_t s) {
-    if (count) launch_persistent(k_query_rays<MODE, true, 1>, p, s, nullptr);
-    else if (p.prio_after == 0) launch_persistent(k_query_rays<MODE, false, 0>, p, s, nullptr);
-    else launch_persistent(k_query_rays<MODE, false, 1>, p, s, nullptr);
+    if (count) launch_persistent(k_query_rays<MODE, true, 1, FILTER>, p, s, nullptr);
+    else if (p.prio_after == 0) launch_persistent(k_query_rays<MODE, false, 0, FILTER>, p, s, nullptr);
+    else launch_persistent(k_query_rays<MODE, false, 1, FILTER>, p, s, nullptr);
+}
+
+template <int MODE>
+void launch_filter(const TraceParams& p, bool count, hipStream_t s) {
+    if (p.q_flags) launch_count<MODE, true>(p, count, s);
+    else launch_count<MODE, false>(p, count, s);
 }
 
 }  // namespace
@@ -80,8 +91,9 @@ void launch_count(const TraceParams& p, bool count, hipStream_t s) {
 hipError_t launch_query_rays(const TraceParams& p, uint32_t mode, bool count, hipStream_t s) {
     if (p.q_n == 0) return hipSuccess;
     if (p.bvh_width != 4 || mode > BM_RAYS_ANY_HIT) return hipErrorInvalidValue;
-    if (mode == BM_RAYS_CLOSEST) launch_count<RAYS_CLOSEST>(p, count, s);
-    else launch_count<RAYS_ANY_HIT>(p, count, s);
+    if ((p.q_flags & BM_RAYS_PAD_MASK) && p.q_ent_n && !p.q_ent) return hipErrorInvalidValue;
+    if (mode == BM_RAYS_CLOSEST) launch_filter<RAYS_CLOSEST>(p, count, s);
+    else launch_filter<RAYS_ANY_HIT>(p, count, s);
     return hipGetLastError();
 }
 

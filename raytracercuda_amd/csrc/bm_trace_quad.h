@@ -189,12 +189,59 @@ __device__ __forceinline__ uint32_t quad_visit_w(const TraceParams& p, uint32_t 
     else return quad_visit(p, node, c, o, inv, tmax, key_t, st, sp);
 }
 
+// ---- ray query filters (beam_c.h BM_RAYS_CULL_* / BM_RAYS_PAD_*) -------------------
+// The filter of a ray query: does the call accept the triangle at sorted index k, which the triangle
+// function has just accepted at distance t within the traversal's current bound? It runs on such
+// candidates only — a few per ray, not one per triangle test — so everything it needs beyond t is
+// fetched or recomputed here and costs the traversal no register: the ray's pad word (read as the
+// flags say) from record `ray` of the batch, the triangle's global id and, for the cull flags, its
+// determinant from its own edges (tri_det: the triangle test's statements). The tests on the call's
+// flags (p.q_flags, wave-uniform) are scalar branches. For BM_RAYS_PAD_MASK the owner of the id is
+// found by a binary search over the first ids of the entries that own triangles (p.q_ent), addressed
+// by 32-bit byte offsets from the wave-uniform base (at most 2^27 entries). A rejected candidate
+// becomes the "no candidate" value before the quad reduction, so it never tightens a bound.
+// ID_LIVE: the caller holds the triangle's global id (closest and multi-hit record it anyway; any hit does not).
+template <bool ID_LIVE>
+__device__ __forceinline__ bool filter_accept(const TraceParams& p, uint32_t ray, uint32_t k, uint32_t id_live,
+                                              const vec3f dir, float t) {
+    const uint32_t flags = p.q_flags;
+    // any hit: the index goes through an empty asm, or the compiler finds the record's address in the kernel's
+    // own load of the ray and keeps that 64-bit address in registers across the whole traversal (12 B of
+    // scratch at 7 waves per SIMD). The other two kernels fit as they are, and the multi-hit one spills with it.
+    if (!ID_LIVE) asm volatile("" : "+v"(ray));
+    const uint32_t pad = reinterpret_cast<const uint32_t*>(p.q_rays)[8 * (size_t)ray + 7];
+    bool ok = t > ((flags & BM_RAYS_PAD_TMIN) ? u2f(pad) : 0.0f);
+    if (flags & (BM_RAYS_CULL_BACK | BM_RAYS_CULL_FRONT)) {
+        const float det = tri_det(p.tris[3 * k + 1], p.tris[3 * k + 2], dir);
+        ok = ok && ((flags & BM_RAYS_CULL_BACK) ? det > 0.0f : det < 0.0f);
+    }
+    if (flags & (BM_RAYS_PAD_SKIP_TRI | BM_RAYS_PAD_MASK)) {
+        const uint32_t id = ID_LIVE ? id_live : f2u(p.tris[3 * k].w);
+        if (flags & BM_RAYS_PAD_SKIP_TRI) {
+            ok = ok && id != pad;
+        } else if (ok) {
+            const char* ent = reinterpret_cast<const char*>(p.q_ent);
+            const uint32_t n = p.q_ent_n;
+            uint32_t lo = 0, hi = n;  // the owner: the last entry whose first id is <= id, in [lo, hi)
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (*reinterpret_cast<const uint32_t*>(ent + (mid << 2)) <= id) lo = mid;
+                else hi = mid;
+            }
+            ok = n != 0 && (*reinterpret_cast<const uint32_t*>(ent + ((n + lo) << 2)) & pad) != 0;
+        }
+    }
+    return ok;
+}
+
 // Closest hit of one ray over the quad (trace_pixel's loop): t > 0, ties to the lowest id.
-template <bool COUNT, uint32_t PRIO, typename QS, int BW = 4>
+// FILTER (ray queries with filter flags; fray: the ray's index in the batch): a candidate is also put to
+// filter_accept. Off, the code is the unfiltered one.
+template <bool COUNT, uint32_t PRIO, typename QS, int BW = 4, bool FILTER = false>
 __device__ __forceinline__ void quad_closest(const TraceParams& p, const QS& st, int c,
                                              const vec3f eye, const vec3f dir, const vec3f inv, float& tbest,
                                              uint32_t& ibest, float& bu, float& bv, unsigned long long& cn,
-                                             unsigned long long& ct) {
+                                             unsigned long long& ct, uint32_t fray = 0) {
     // One iteration: the pending leaf (if any), then the pop that follows it, then the node visit —
     // a leaf and the next node share an iteration (one loop overhead and one divergent pass fewer
     // per leaf); the per-ray sequence of leaf tests, pops and node visits is trace_pixel's.
@@ -215,7 +262,9 @@ __device__ __forceinline__ void quad_closest(const TraceParams& p, const QS& st,
                     // pieces was measured against this and not kept: DESIGN.md §5)
                     const float4 a = p.tris[3 * k + 0], b = p.tris[3 * k + 1], cc = p.tris[3 * k + 2];
                     float tt, uu, vv;
-                    if (tri_test(a, b, cc, eye, dir, tt, uu, vv) && tt > 0.0f && tt < 3.40282347e+38f) {
+                    bool acc = tri_test(a, b, cc, eye, dir, tt, uu, vv) && tt > 0.0f && tt < 3.40282347e+38f;
+                    if constexpr (FILTER) acc = acc && tt <= tbest && filter_accept<true>(p, fray, k, f2u(a.w), dir, tt);
+                    if (acc) {
                         t = tt;
                         id = f2u(a.w);
                         u = uu;
@@ -266,10 +315,11 @@ __device__ __forceinline__ void quad_closest(const TraceParams& p, const QS& st,
 // Any-hit segment o + s*d, 0 < s < 1 (shadow_ray's loop). Within a leaf the triangles are tested
 // four at a time; the counter takes the tests up to the first occluder in leaf order, as the
 // sequential loop of orc_bvh_shadow stops there.
-template <bool COUNT, uint32_t PRIO, typename QS, int BW = 4>
+// FILTER, fray: as in quad_closest; an occluder is a triangle the filter accepts.
+template <bool COUNT, uint32_t PRIO, typename QS, int BW = 4, bool FILTER = false>
 __device__ __forceinline__ bool quad_anyhit(const TraceParams& p, const QS& st, int c,
                                             const vec3f o, const vec3f d, unsigned long long& cn,
-                                            unsigned long long& ct) {
+                                            unsigned long long& ct, uint32_t fray = 0) {
     const vec3f inv = v3(1.f / d.x, 1.f / d.y, 1.f / d.z);
     int sp = 0;
     uint32_t next = 0, iter = 0;
@@ -283,8 +333,13 @@ __device__ __forceinline__ bool quad_anyhit(const TraceParams& p, const QS& st, 
                 if (k0 + c < cnt) {
                     float t, u, v;
                     if (tri_test(p.tris[3 * k + 0], p.tris[3 * k + 1], p.tris[3 * k + 2], o, d, t, u, v) &&
-                        t > 0.0f && t < 1.0f)
-                        occ_at = (uint32_t)c;
+                        t > 0.0f && t < 1.0f) {
+                        if constexpr (FILTER) {
+                            if (filter_accept<false>(p, fray, k, 0u, d, t)) occ_at = (uint32_t)c;
+                        } else {
+                            occ_at = (uint32_t)c;
+                        }
+                    }
                 }
                 occ_at = min(occ_at, dpp_u<QP_X1>(occ_at));
                 occ_at = min(occ_at, dpp_u<QP_X2>(occ_at));
