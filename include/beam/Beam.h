@@ -282,6 +282,14 @@ class IScene {
                            uint32_t* deviceCounts = nullptr) {
         return (u32)bm_scene_closest_points_multi(h_, devicePoints, n, k, flags, deviceHits, deviceCounts);
     }
+    // Extension: the triangles that intersect each of n axis-aligned boxes in device memory
+    // (bm_scene_overlap_boxes; asynchronous on the context stream). mode BM_BOXES_COUNT: deviceOut is
+    // uint32_t[n]; BM_BOXES_ANY: uint8_t[n]; BM_BOXES_LIST: the ids go to deviceIds at the segments of
+    // deviceOffsets (n + 1 ascending values), the counts to deviceOut unless it is null.
+    u32 overlapBoxes(const bm_box* deviceBoxes, u32 n, u32 mode, void* deviceOut,
+                     const uint32_t* deviceOffsets = nullptr, uint32_t* deviceIds = nullptr) {
+        return (u32)bm_scene_overlap_boxes(h_, deviceBoxes, n, mode, 0, deviceOut, deviceOffsets, deviceIds);
+    }
     // Extension: instance transforms (include/beam_c.h, "instance transforms"). xform: 12 floats, row-major
     // 3x4 (xformFromColumnMajor4x4 converts a glm::mat4's 16 floats). addInstance appends the mesh at that
     // placement and reports the entry's index; setInstanceTransform takes effect at the next updateGPUScene

@@ -542,6 +542,85 @@ int32_t bm_scene_closest_points_multi_counters(bm_scene* s, const bm_point* poin
                                                uint32_t flags, bm_hit* hits_dev, uint32_t* counts_dev,
                                                uint64_t out[4]);
 
+/* ---- box overlap queries: the triangles that intersect each box of a batch ---------------------
+ * The third family beside rays and points: volumes. For axis-aligned box i: which triangles of the
+ * scene touch it — voxelising a mesh into an occupancy grid, selecting a region, the broad phase of
+ * box colliders and triggers, binning triangles into cells, bricks or clusters, clipping work to a
+ * region of interest. An unordered traversal of the same BVH4 that follows every child box the query
+ * box meets.
+ * boxes_dev is a device pointer on the context's device, 16-byte aligned; out_dev, offsets_dev and
+ * ids_dev are 4-byte aligned (the byte plane of BM_BOXES_ANY: any address). The work is enqueued on the
+ * context stream and the call returns without waiting; bm_sync waits. On a multi-device context the
+ * query runs on the root device alone.
+ * For box i with centre c and half-size h, O_i is the set of ALL triangles g of the scene that
+ *   tri_box(c, h, tv) accepts, tv being the triangle as the build's 48-byte record holds it: v0, and
+ *   v1 = v0 + e1, v2 = v0 + e2 with e1, e2 the record's edges, one float32 addition per component.
+ *   (The record's edges are the mesh's v1 - v0 and v2 - v0 in float32, so v1 and v2 differ from the
+ *   mesh's own v1 and v2 only where that subtraction was inexact.) The test is inclusive: a triangle
+ *   touching a face of the box is in O_i.
+ * tri_box is the reference's triBoxOverlap, the test its kd-tree and hashed grid sort triangles by, in
+ *   float32, one rounding per operation in the order written, never contracted; a comparison with NaN
+ *   is false. With x, y, z the components 0, 1, 2:
+ *     w0 = v0 - c   w1 = v1 - c   w2 = v2 - c            (per component)
+ *     f0 = w1 - w0  f1 = w2 - w1  f2 = w0 - w2           (per component)
+ *     sep(pa, pb, rad): with mn, mx = (pa < pb) ? (pa, pb) : (pb, pa):   mn > rad || mx < -rad
+ *     X(f, a, b):  sep(f.z*a.y - f.y*a.z,   f.z*b.y - f.y*b.z,   |f.z|*h.y + |f.y|*h.z)
+ *     Y(f, a, b):  sep(-f.z*a.x + f.x*a.z, -f.z*b.x + f.x*b.z,  |f.z|*h.x + |f.x|*h.z)
+ *     Z(f, a, b):  sep(f.y*b.x - f.x*b.y,   f.y*a.x - f.x*a.y,   |f.y|*h.x + |f.x|*h.y)   (b's value first)
+ *     Z0(f, a, b): sep(f.y*a.x - f.x*a.y,   f.y*b.x - f.x*b.y,   |f.y|*h.x + |f.x|*h.y)
+ *     the nine cross-axis tests:  X(f0, w0, w2)  Y(f0, w0, w2)  Z(f0, w1, w2)
+ *                                 X(f1, w0, w2)  Y(f1, w0, w2)  Z0(f1, w0, w1)
+ *                                 X(f2, w0, w1)  Y(f2, w0, w1)  Z(f2, w1, w2)
+ *     the AABB test, per axis k:  mn = mx = w0.k; if (w1.k < mn) mn = w1.k; if (w1.k > mx) mx = w1.k;
+ *                                 the same with w2.k;   mn > h.k || mx < -h.k
+ *     the plane test:  nrm = (f0.y*f1.z - f0.z*f1.y, f0.z*f1.x - f0.x*f1.z, f0.x*f1.y - f0.y*f1.x);
+ *                      per axis k: nrm.k > 0 ? (lo.k = -h.k - w0.k, hi.k = h.k - w0.k)
+ *                                            : (lo.k = h.k - w0.k, hi.k = -h.k - w0.k);
+ *                      passes when !(dot(nrm, lo) > 0) && dot(nrm, hi) >= 0,
+ *                      dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *   tri_box accepts when none of the nine cross-axis tests and none of the three AABB tests is true and
+ *   the plane test passes. (-f.z*a.x is the product of the negated f.z.) A zero-area triangle has a
+ *   zero normal and zero radii on the axes of its vanished edges: it is accepted when the remaining
+ *   tests do not separate it, so a point-like or segment-like triangle inside a box is in O_i.
+ * mode BM_BOXES_COUNT: out_dev is uint32_t[n], out_dev[i] = |O_i|. offsets_dev and ids_dev are ignored.
+ * mode BM_BOXES_ANY: out_dev is uint8_t[n], out_dev[i] = 1 when O_i is not empty, else 0. The traversal
+ *   of a box ends at the first accepted triangle.
+ * mode BM_BOXES_LIST: a CSR (compressed sparse row) fill. offsets_dev is uint32_t[n + 1], ascending:
+ *   normally the exclusive prefix sum of a count pass, but any segmentation is allowed (i * stride, say).
+ *   The ids of O_i are written to ids_dev[offsets_dev[i] ..], at most offsets_dev[i+1] - offsets_dev[i]
+ *   of them; nothing is ever written outside a box's own segment, and the unused tail of a segment is
+ *   left untouched. out_dev may be NULL; otherwise it is uint32_t[n] and out_dev[i] = |O_i|, so a caller
+ *   whose segments were too short can tell. The order inside a segment is the traversal's: the same for
+ *   every call on the same build, on every GPU and grid size (nothing is decided by an atomic), and
+ *   otherwise unspecified. When a segment is too short it holds the first ids of that order.
+ * Invalid boxes (a non-finite component of c or h; a component of h that is negative or NaN) are not
+ *   looked up: count 0, byte 0, no ids. h = 0 is valid (the box is a point). The pad words are ignored.
+ *   Over an empty built scene every count and byte is 0.
+ * flags: none defined yet, pass 0. Boxes are taken in the order given, 16 consecutive boxes per wave.
+ * BM_ERROR_INVALID_PARAMETER: a null handle; with n > 0 a null boxes_dev, a null out_dev unless the mode
+ * is BM_BOXES_LIST, a null offsets_dev or ids_dev with BM_BOXES_LIST; a misaligned pointer; an unknown
+ * mode or flag bit; a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT: the scene has
+ * no current build. n = 0 succeeds without a launch. */
+typedef struct bm_box {
+    float center[3];
+    uint32_t pad0;
+    float half[3];
+    uint32_t pad1;
+} bm_box; /* 32 B */
+#define BM_BOXES_COUNT 0u
+#define BM_BOXES_ANY 1u
+#define BM_BOXES_LIST 2u
+int32_t bm_scene_overlap_boxes(bm_scene* s, const bm_box* boxes_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                               void* out_dev, const uint32_t* offsets_dev, uint32_t* ids_dev);
+/* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle tests (a leaf's
+ * triangle count per leaf reached), out[2] the sum of |O_i| (BM_BOXES_ANY: the number of boxes with a
+ * hit), out[3] the largest number of stack entries any box held at once (above 24 the traversal used the
+ * global overflow area); invalid boxes count nothing. Results are written exactly as
+ * bm_scene_overlap_boxes writes them. Synchronous. */
+int32_t bm_scene_overlap_boxes_counters(bm_scene* s, const bm_box* boxes_dev, uint32_t n, uint32_t mode,
+                                        uint32_t flags, void* out_dev, const uint32_t* offsets_dev,
+                                        uint32_t* ids_dev, uint64_t out[4]);
+
 /* ---- hit attributes: the meshes' vertex slots interpolated at ray-query hits ------------------
  * The reference's bmFaceInterpolate<T>(face, u, v, meshData, dataIdx) (CudaComon.cuh:253-266) over n
  * bm_hit records in device memory (as bm_scene_trace_rays writes them, or made by the caller): what a

@@ -105,6 +105,14 @@ class Point(C.Structure):
     _fields_ = [("p", C.c_float * 3), ("rmax", C.c_float)]
 
 
+class Box(C.Structure):
+    """bm_box: one axis-aligned box of bm_scene_overlap_boxes (32 bytes)."""
+    _fields_ = [("center", C.c_float * 3), ("pad0", C.c_uint32), ("half", C.c_float * 3), ("pad1", C.c_uint32)]
+
+
+BOXES_COUNT, BOXES_ANY, BOXES_LIST = 0, 1, 2  # its modes
+
+
 class AttrReq(C.Structure):
     """bm_attr_req: one request of bm_scene_hit_attributes (24 bytes)."""
     _fields_ = [("slot", C.c_uint32), ("components", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32),
@@ -187,6 +195,8 @@ SIGNATURES = {
     "bm_scene_closest_points_counters": (_I, [_P, _P, _U, _U, _P, _U64P]),
     "bm_scene_closest_points_multi": (_I, [_P, _P, _U, _U, _U, _P, _P]),
     "bm_scene_closest_points_multi_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _U64P]),
+    "bm_scene_overlap_boxes": (_I, [_P, _P, _U, _U, _U, _P, _P, _P]),
+    "bm_scene_overlap_boxes_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _U64P]),
     "bm_scene_hit_attributes": (_I, [_P, _P, _U, C.POINTER(AttrReq), _U]),
     "bm_camera_create": (_I, [_P, C.POINTER(_P)]),
     "bm_camera_set_initial_rays": (_I, [_P, _U, _U, _F, _F, _F, _F, _F]),

@@ -641,6 +641,129 @@ class IScene:
             res["counters"] = cnt
         return res
 
+    def overlapBoxesDevice(self, boxes_ptr: int, n: int, mode: int, out_ptr: int, offsets_ptr: int = 0,
+                           ids_ptr: int = 0, flags: int = 0, counters=None) -> int:
+        """bm_scene_overlap_boxes on device pointers (n bm_box records of 32 bytes in, 16-byte aligned; out_ptr:
+        n uint32 for BOXES_COUNT and BOXES_LIST (there it may be 0), n bytes for BOXES_ANY; BOXES_LIST:
+        offsets_ptr n + 1 uint32, ids_ptr the id segments); returns the error code. Asynchronous on the
+        context stream unless `counters` (a uint64[4] numpy array to fill) is given. flags: none defined yet."""
+        bp, op = C.c_void_p(boxes_ptr or None), C.c_void_p(out_ptr or None)
+        fp, ip = C.c_void_p(offsets_ptr or None), C.c_void_p(ids_ptr or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_overlap_boxes(self.h, bp, n, mode, flags, op, fp, ip)
+        return self.ctx.lib.bm_scene_overlap_boxes_counters(self.h, bp, n, mode, flags, op, fp, ip,
+                                                            counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def overlapBoxes(self, centers, halves=None, mode: str = "count", counters: bool = False):
+        """The triangles that intersect each of n axis-aligned boxes (bm_scene_overlap_boxes): a triangle is in
+        a box's set when the reference's triangle/box test accepts it, faces inclusive. centers (n,3) and halves
+        (n,3) (or one (3,) half-size for all), or one packed (n,8) float32 array (centre, pad, half, pad).
+
+        mode "count": {"count": (n,)} the number of triangles per box. mode "any": {"any": (n,) bool}.
+        mode "list": the count pass, torch.cumsum of the counts into offsets on the device, one read of the
+        total to size ids, then the list pass: {"count": (n,), "offsets": (n + 1,), "ids": (total,)} with box
+        i's triangle ids in ids[offsets[i]:offsets[i + 1]], in traversal order (the same on every call).
+
+        numpy in: uploads, queries and waits; returns numpy arrays (uint32; "any" bool).
+        torch tensors on the context's device: everything stays on the device (int32; "any" bool); "list"
+        waits once, for the total. Make the context on torch's stream, as for traceRays.
+        counters=True adds "counters": [node records, triangle tests, the sum of the counts (any: boxes with a
+        hit), deepest stack] of the last pass (waits)."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        modes = {"count": _lib.BOXES_COUNT, "any": _lib.BOXES_ANY, "list": _lib.BOXES_LIST}
+        if mode not in modes:
+            raise BeamError(ERROR_INVALID_PARAMETER, 'overlapBoxes: mode is "count", "any" or "list"')
+        on_device = isinstance(centers, torch.Tensor)
+        if on_device:
+            if centers.dim() == 2 and centers.shape[1] == 8 and halves is None:
+                boxes = centers
+            elif centers.dim() == 2 and centers.shape[1] == 3 and halves is not None:
+                boxes = torch.zeros((centers.shape[0], 8), dtype=torch.float32, device=centers.device)
+                boxes[:, 0:3] = centers
+                boxes[:, 4:7] = halves
+            else:
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                "overlapBoxes: centers (n, 3) with halves, or packed (n, 8), float32")
+            if boxes.device != dev or boxes.dtype != torch.float32 or not boxes.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"overlapBoxes: boxes must be contiguous float32 on {dev} (the context's device)")
+        else:
+            a = _f32(centers)
+            if halves is None:
+                packed = np.ascontiguousarray(a.reshape(-1, 8))
+            else:
+                ctr = a.reshape(-1, 3)
+                packed = np.zeros((ctr.shape[0], 8), np.float32)
+                packed[:, 0:3] = ctr
+                packed[:, 4:7] = _f32(halves).reshape(-1, 3)
+            boxes = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = boxes.shape[0]
+        bptr = boxes.data_ptr() if n else 0
+        cnt = np.zeros(4, np.uint64) if counters else None
+        if mode == "any":
+            out = torch.empty((n,), dtype=torch.uint8, device=dev)
+            self.ctx._check(self.overlapBoxesDevice(bptr, n, _lib.BOXES_ANY, out.data_ptr() if n else 0, counters=cnt))
+            res = {"any": out.view(torch.bool)}
+        else:
+            count = torch.empty((n,), dtype=torch.int32, device=dev)
+            if mode == "count":
+                self.ctx._check(self.overlapBoxesDevice(bptr, n, _lib.BOXES_COUNT, count.data_ptr() if n else 0,
+                                                        counters=cnt))
+                res = {"count": count}
+            else:
+                self.ctx._check(self.overlapBoxesDevice(bptr, n, _lib.BOXES_COUNT, count.data_ptr() if n else 0))
+                if not on_device:
+                    self.ctx.sync()  # the counts, before torch's stream reads them
+                offsets = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
+                torch.cumsum(count, 0, dtype=torch.int32, out=offsets[1:])
+                total = int(offsets[-1].item())  # the one read; it also puts the offsets before the list pass
+                ids = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)  # never a null pointer
+                self.ctx._check(self.overlapBoxesDevice(bptr, n, _lib.BOXES_LIST, 0, offsets.data_ptr(),
+                                                        ids.data_ptr(), counters=cnt))
+                res = {"count": count, "offsets": offsets, "ids": ids[:total]}
+        self._boxes_keep = boxes  # until the next query: the kernel may not have read them yet
+        if not on_device:
+            self.ctx.sync()
+            res = {k: (v.cpu().numpy() if k == "any" else v.cpu().numpy().view(np.uint32)) for k, v in res.items()}
+        if counters:
+            res["counters"] = cnt
+        return res
+
+    def voxelize(self, lo, hi, dims):
+        """Occupancy of a regular grid: a bool tensor of shape dims = (nx, ny, nz) on the context's device, True
+        where a triangle intersects the cell (overlapBoxes mode "any" over the grid's cells; the cells are made
+        on torch's current stream, which is waited for before the query goes onto the context stream; the
+        result is written in context-stream order: make the context on torch's stream, as for traceRays, or
+        call Context.sync() before reading it).
+        The cells, in float32 (numpy statements; every operation rounds once):
+            lo32, hi32 = np.float32(lo), np.float32(hi)
+            cell = (hi32 - lo32) / np.float32(dims)                              # (3,)
+            half = np.float32(0.5) * cell                                        # (3,), every cell's half-size
+            centre[i, j, k] = lo32 + (np.float32((i, j, k)) + np.float32(0.5)) * cell
+        Cell (i, j, k) is box (i * ny + j) * nz + k of the batch."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        dims = tuple(int(d) for d in dims)
+        if len(dims) != 3 or min(dims) < 1:
+            raise BeamError(ERROR_INVALID_PARAMETER, "voxelize: dims is three positive integers")
+        lo32, hi32 = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        cell = (hi32 - lo32) / np.asarray(dims, np.float32)
+        half = np.float32(0.5) * cell
+        n = dims[0] * dims[1] * dims[2]
+        boxes = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+        grid = boxes.view(dims[0], dims[1], dims[2], 8)
+        for a in range(3):  # one multiply and one add per component, as the statements above
+            idx = torch.arange(dims[a], dtype=torch.float32, device=dev)
+            axis = float(lo32[a]) + (idx + 0.5) * float(cell[a])
+            shape = [1, 1, 1]
+            shape[a] = dims[a]
+            grid[..., a] = axis.view(shape)
+            grid[..., 4 + a] = float(half[a])
+        torch.cuda.current_stream(dev).synchronize()  # the cells, before the context stream reads them
+        return self.overlapBoxes(boxes, mode="any")["any"].view(dims)
+
     def closestPointsDevice(self, points_ptr: int, n: int, out_ptr: int, counters=None, flags=0) -> int:
         """bm_scene_closest_points on device pointers (n bm_point records of 16 bytes in, n bm_hit records of
         16 bytes out, both 16-byte aligned); returns the error code. Asynchronous on the context stream unless

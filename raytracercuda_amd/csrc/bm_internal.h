@@ -244,6 +244,14 @@ hipError_t launch_query_multi(const TraceParams& p, bool count_all, bool count, 
 // triangle within rmax; set up as for launch_closest_points. count: into p.counters[0..3] (node records,
 // triangle evaluations, the sum of the per-point counts, the deepest stack held).
 hipError_t launch_closest_points_multi(const TraceParams& p, bool count_all, bool count, hipStream_t s);
+// Box overlap query (bm_boxes.hip): the triangles tri_box accepts for each of p.q_n boxes, two float4
+// (centre, pad) (half, pad) each in p.q_rays; set up as for launch_closest_points. mode BM_BOXES_COUNT: one
+// uint32 per box into p.q_out; BM_BOXES_ANY: one byte; BM_BOXES_LIST: the ids into p.q_counts at the
+// segments p.q_ent[i] .. p.q_ent[i + 1] (q_n + 1 ascending offsets; the two fields serve here under their
+// ray-query names so that TraceParams, and with it every other kernel's argument block, stays as it is) and,
+// where p.q_out is not null, the counts there. count: into p.counters[0..3] (node records, triangle tests,
+// the sum of the counts, the deepest stack held).
+hipError_t launch_overlap_boxes(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
 // ---- hit attributes (bm_attrs.hip): vertex slots interpolated at the hits of a ray query ------------
 // One entry per scene mesh, in scene order: every slot's device buffer (null: the mesh has none), so the
 // table depends on the meshes alone and not on what a call requests.
