@@ -290,6 +290,13 @@ class IScene {
                      const uint32_t* deviceOffsets = nullptr, uint32_t* deviceIds = nullptr) {
         return (u32)bm_scene_overlap_boxes(h_, deviceBoxes, n, mode, 0, deviceOut, deviceOffsets, deviceIds);
     }
+    // Extension: the scene triangles that intersect each of n query triangles in device memory
+    // (bm_scene_overlap_triangles; asynchronous on the context stream). Modes and outputs as overlapBoxes
+    // with BM_TRIS_*; flags 0 or BM_TRIS_PAD_SKIP_TRI (pad0 of each record: an id that is never reported).
+    u32 overlapTriangles(const bm_tri* deviceTris, u32 n, u32 mode, void* deviceOut,
+                         const uint32_t* deviceOffsets = nullptr, uint32_t* deviceIds = nullptr, u32 flags = 0) {
+        return (u32)bm_scene_overlap_triangles(h_, deviceTris, n, mode, flags, deviceOut, deviceOffsets, deviceIds);
+    }
     // Extension: instance transforms (include/beam_c.h, "instance transforms"). xform: 12 floats, row-major
     // 3x4 (xformFromColumnMajor4x4 converts a glm::mat4's 16 floats). addInstance appends the mesh at that
     // placement and reports the entry's index; setInstanceTransform takes effect at the next updateGPUScene

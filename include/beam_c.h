@@ -621,6 +621,88 @@ int32_t bm_scene_overlap_boxes_counters(bm_scene* s, const bm_box* boxes_dev, ui
                                         uint32_t flags, void* out_dev, const uint32_t* offsets_dev,
                                         uint32_t* ids_dev, uint64_t out[4]);
 
+/* ---- triangle overlap queries: the scene triangles each triangle of a batch intersects ----------
+ * The volume family's mesh-against-mesh question: a collider that is a mesh and not a box, a tool swept
+ * through a part, the intersection curve a boolean operation starts from, the self-intersections mesh
+ * repair looks for. For query triangle i: which triangles of the scene it touches. An unordered
+ * traversal of the same BVH4 that follows every child box the query triangle's own bounds meet.
+ * tris_dev is a device pointer on the context's device, 16-byte aligned; out_dev, offsets_dev and
+ * ids_dev are 4-byte aligned (the byte plane of BM_TRIS_ANY: any address). The work is enqueued on the
+ * context stream and the call returns without waiting; bm_sync waits. On a multi-device context the
+ * query runs on the root device alone.
+ * For query triangle a (vertices a0, a1, a2), O_i is the set of ALL triangles g of the scene that
+ *   tri_tri(a, b) accepts, b being g as the build's 48-byte record holds it: b0 = v0, b1 = v0 + e1,
+ *   b2 = v0 + e2 with e1, e2 the record's edges, one float32 addition per component (as for
+ *   bm_scene_overlap_boxes). The test is inclusive: triangles that touch intersect.
+ * tri_tri is a separating-axis test in float32, one rounding per operation in the order written, never
+ *   contracted; a comparison with NaN is false. With x, y, z the components 0, 1, 2:
+ *     the AABB part, on the raw coordinates, per axis k:
+ *       qlo = qhi = a0.k; if (a1.k < qlo) qlo = a1.k; if (a1.k > qhi) qhi = a1.k; the same with a2.k;
+ *       blo, bhi likewise from b0.k, b1.k, b2.k;         meets.k:  blo <= qhi && bhi >= qlo
+ *     the separating-axis part, on coordinates translated by a0 (so that a scene far from the origin
+ *     keeps the test's resolution), per component:
+ *       p1 = a1 - a0   p2 = a2 - a0   (p0 = 0)           q0 = b0 - a0   q1 = b1 - a0   q2 = b2 - a0
+ *       eA0 = p1   eA1 = p2 - p1   eA2 = 0 - p2          eB0 = q1 - q0  eB1 = q2 - q1  eB2 = q0 - q2
+ *       cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x)
+ *       dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z
+ *       nA = cross(eA0, eA1)   nB = cross(eB0, eB1)
+ *       sep(d): s1 = dot(d, p1), s2 = dot(d, p2); mnA = mxA = 0; if (s1 < mnA) mnA = s1;
+ *               if (s1 > mxA) mxA = s1; the same with s2;
+ *               t0 = dot(d, q0), t1 = dot(d, q1), t2 = dot(d, q2); mnB = mxB = t0; if (t1 < mnB) mnB = t1;
+ *               if (t1 > mxB) mxB = t1; the same with t2;        mxA < mnB || mxB < mnA
+ *       the seventeen axes, in this order: nA; nB; cross(eA_i, eB_j) for i = 0..2 (outer), j = 0..2;
+ *       cross(nA, eA_i) for i = 0..2; cross(nB, eB_j) for j = 0..2
+ *   tri_tri accepts when meets.k holds on all three axes and sep(d) is false for all seventeen axes.
+ *   An axis that vanishes (parallel edges, a zero normal) projects everything to 0 and separates
+ *   nothing, so degenerate triangles of either side (point-like, segment-like) are accepted exactly when
+ *   the remaining axes do not separate them. The six in-plane axes cross(n, e) are what reject coplanar
+ *   triangles that lie apart. The translation makes the test not bit-symmetric: tri_tri(a, b) and
+ *   tri_tri(b, a) can differ by roundings at contact.
+ * mode BM_TRIS_COUNT: out_dev is uint32_t[n], out_dev[i] = |O_i|. offsets_dev and ids_dev are ignored.
+ * mode BM_TRIS_ANY: out_dev is uint8_t[n], out_dev[i] = 1 when O_i is not empty, else 0. The traversal
+ *   of a query ends at the first accepted triangle.
+ * mode BM_TRIS_LIST: a CSR (compressed sparse row) fill, by BM_BOXES_LIST's rules. offsets_dev is
+ *   uint32_t[n + 1], ascending: normally the exclusive prefix sum of a count pass, but any segmentation
+ *   is allowed. The ids of O_i are written to ids_dev[offsets_dev[i] ..], at most
+ *   offsets_dev[i+1] - offsets_dev[i] of them; nothing is ever written outside a query's own segment,
+ *   and the unused tail of a segment is left untouched. out_dev may be NULL; otherwise it is uint32_t[n]
+ *   and out_dev[i] = |O_i|. The order inside a segment is the traversal's: the same for every call on
+ *   the same build, on every GPU and grid size (nothing is decided by an atomic), and otherwise
+ *   unspecified. When a segment is too short it holds the first ids of that order.
+ * Invalid query triangles (any non-finite vertex component) are not looked up: count 0, byte 0, no ids.
+ *   Degenerate query triangles are valid. Over an empty built scene every count and byte is 0.
+ * flags: 0, or BM_TRIS_PAD_SKIP_TRI: pad0 of each record names one triangle id that is never in O_i
+ *   (a mesh queried against itself passes each triangle's own id). The filter runs on candidates the
+ *   test has accepted, as the ray filters do; NO_TRI (0xFFFFFFFF) or an id past the scene skips nothing.
+ *   Without the flag the pad words are ignored; pad1 and pad2 always are.
+ * Queries are taken in the order given, 16 consecutive triangles per wave.
+ * BM_ERROR_INVALID_PARAMETER: a null handle; with n > 0 a null tris_dev, a null out_dev unless the mode
+ * is BM_TRIS_LIST, a null offsets_dev or ids_dev with BM_TRIS_LIST; a misaligned pointer; an unknown
+ * mode or flag bit; a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT: the scene has
+ * no current build. n = 0 succeeds without a launch. */
+typedef struct bm_tri {
+    float v0[3];
+    uint32_t pad0;
+    float v1[3];
+    uint32_t pad1;
+    float v2[3];
+    uint32_t pad2;
+} bm_tri; /* 48 B */
+#define BM_TRIS_COUNT 0u
+#define BM_TRIS_ANY 1u
+#define BM_TRIS_LIST 2u
+#define BM_TRIS_PAD_SKIP_TRI 1u /* flag: pad0 is a triangle id that is never in O_i */
+int32_t bm_scene_overlap_triangles(bm_scene* s, const bm_tri* tris_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                                   void* out_dev, const uint32_t* offsets_dev, uint32_t* ids_dev);
+/* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle tests (a leaf's
+ * triangle count per leaf reached), out[2] the sum of |O_i| (BM_TRIS_ANY: the number of queries with a
+ * hit), out[3] the largest number of stack entries any query held at once (above 24 the traversal used
+ * the global overflow area); invalid queries count nothing. Results are written exactly as
+ * bm_scene_overlap_triangles writes them. Synchronous. */
+int32_t bm_scene_overlap_triangles_counters(bm_scene* s, const bm_tri* tris_dev, uint32_t n, uint32_t mode,
+                                            uint32_t flags, void* out_dev, const uint32_t* offsets_dev,
+                                            uint32_t* ids_dev, uint64_t out[4]);
+
 /* ---- hit attributes: the meshes' vertex slots interpolated at ray-query hits ------------------
  * The reference's bmFaceInterpolate<T>(face, u, v, meshData, dataIdx) (CudaComon.cuh:253-266) over n
  * bm_hit records in device memory (as bm_scene_trace_rays writes them, or made by the caller): what a

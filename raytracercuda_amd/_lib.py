@@ -113,6 +113,16 @@ class Box(C.Structure):
 BOXES_COUNT, BOXES_ANY, BOXES_LIST = 0, 1, 2  # its modes
 
 
+class Tri(C.Structure):
+    """bm_tri: one query triangle of bm_scene_overlap_triangles (48 bytes)."""
+    _fields_ = [("v0", C.c_float * 3), ("pad0", C.c_uint32), ("v1", C.c_float * 3), ("pad1", C.c_uint32),
+                ("v2", C.c_float * 3), ("pad2", C.c_uint32)]
+
+
+TRIS_COUNT, TRIS_ANY, TRIS_LIST = 0, 1, 2  # its modes
+TRIS_PAD_SKIP_TRI = 1  # its flag: pad0 is a triangle id that is never reported
+
+
 class AttrReq(C.Structure):
     """bm_attr_req: one request of bm_scene_hit_attributes (24 bytes)."""
     _fields_ = [("slot", C.c_uint32), ("components", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32),
@@ -197,6 +207,8 @@ SIGNATURES = {
     "bm_scene_closest_points_multi_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _U64P]),
     "bm_scene_overlap_boxes": (_I, [_P, _P, _U, _U, _U, _P, _P, _P]),
     "bm_scene_overlap_boxes_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _U64P]),
+    "bm_scene_overlap_triangles": (_I, [_P, _P, _U, _U, _U, _P, _P, _P]),
+    "bm_scene_overlap_triangles_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _U64P]),
     "bm_scene_hit_attributes": (_I, [_P, _P, _U, C.POINTER(AttrReq), _U]),
     "bm_camera_create": (_I, [_P, C.POINTER(_P)]),
     "bm_camera_set_initial_rays": (_I, [_P, _U, _U, _F, _F, _F, _F, _F]),

@@ -764,6 +764,143 @@ class IScene:
         torch.cuda.current_stream(dev).synchronize()  # the cells, before the context stream reads them
         return self.overlapBoxes(boxes, mode="any")["any"].view(dims)
 
+    def overlapTrianglesDevice(self, tris_ptr: int, n: int, mode: int, out_ptr: int, offsets_ptr: int = 0,
+                               ids_ptr: int = 0, flags: int = 0, counters=None) -> int:
+        """bm_scene_overlap_triangles on device pointers (n bm_tri records of 48 bytes in, 16-byte aligned;
+        out_ptr: n uint32 for TRIS_COUNT and TRIS_LIST (there it may be 0), n bytes for TRIS_ANY; TRIS_LIST:
+        offsets_ptr n + 1 uint32, ids_ptr the id segments); returns the error code. Asynchronous on the context
+        stream unless `counters` (a uint64[4] numpy array to fill) is given. flags: 0 or TRIS_PAD_SKIP_TRI."""
+        tp, op = C.c_void_p(tris_ptr or None), C.c_void_p(out_ptr or None)
+        fp, ip = C.c_void_p(offsets_ptr or None), C.c_void_p(ids_ptr or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_overlap_triangles(self.h, tp, n, mode, flags, op, fp, ip)
+        return self.ctx.lib.bm_scene_overlap_triangles_counters(self.h, tp, n, mode, flags, op, fp, ip,
+                                                                counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def overlapTriangles(self, tris, mode: str = "count", skip_tri=None, counters: bool = False):
+        """The scene triangles that intersect each of n query triangles (bm_scene_overlap_triangles): a scene
+        triangle is in a query's set when the header's triangle/triangle test accepts the pair, touching
+        included. tris: (n, 3, 3) vertex positions, or packed (n, 12) float32 bm_tri records (v0, pad0, v1,
+        pad1, v2, pad2). skip_tri: None, or n triangle ids (one per query) that are never reported — each
+        triangle's own id when a mesh is queried against itself; 0xFFFFFFFF (-1) skips nothing. With packed
+        records and skip_tri=True the records' own pad0 words are the ids.
+
+        Modes, results, numpy and torch behaviour and `counters` exactly as overlapBoxes: "count" {"count"},
+        "any" {"any"}, "list" {"count", "offsets", "ids"} after a count pass and torch.cumsum on the device."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        modes = {"count": _lib.TRIS_COUNT, "any": _lib.TRIS_ANY, "list": _lib.TRIS_LIST}
+        if mode not in modes:
+            raise BeamError(ERROR_INVALID_PARAMETER, 'overlapTriangles: mode is "count", "any" or "list"')
+        on_device = isinstance(tris, torch.Tensor)
+        own_pad = skip_tri is True
+        if on_device:
+            if tris.device != dev or tris.dtype != torch.float32:
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"overlapTriangles: tris must be float32 on {dev} (the context's device)")
+            if tris.dim() == 2 and tris.shape[1] == 12 and tris.is_contiguous() and (skip_tri is None or own_pad):
+                rec = tris
+            elif (tris.dim() == 3 and tris.shape[1:] == (3, 3)) or (tris.dim() == 2 and tris.shape[1] == 12):
+                rec = torch.zeros((tris.shape[0], 12), dtype=torch.float32, device=dev)
+                rec.view(-1, 3, 4)[:, :, 0:3] = tris if tris.dim() == 3 else tris.view(-1, 3, 4)[:, :, 0:3]
+            else:
+                raise BeamError(ERROR_INVALID_PARAMETER, "overlapTriangles: tris (n, 3, 3), or packed (n, 12)")
+            if skip_tri is not None and not own_pad:
+                sk = skip_tri if isinstance(skip_tri, torch.Tensor) else torch.from_numpy(
+                    np.ascontiguousarray(skip_tri).astype(np.int64).astype(np.uint32).view(np.int32))
+                rec.view(torch.int32)[:, 3] = sk.to(device=dev, dtype=torch.int32).reshape(-1)
+        else:
+            a = _f32(tris)
+            if a.ndim == 2 and a.shape[1] == 12:
+                packed = np.ascontiguousarray(a).copy()
+            else:
+                packed = np.zeros((a.reshape(-1, 3, 3).shape[0], 12), np.float32)
+                packed.reshape(-1, 3, 4)[:, :, 0:3] = a.reshape(-1, 3, 3)
+            if skip_tri is not None and not own_pad:
+                packed.view(np.uint32)[:, 3] = np.asarray(skip_tri).astype(np.int64).astype(np.uint32).reshape(-1)
+            rec = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        flags = _lib.TRIS_PAD_SKIP_TRI if skip_tri is not None else 0
+        n = rec.shape[0]
+        tptr = rec.data_ptr() if n else 0
+        cnt = np.zeros(4, np.uint64) if counters else None
+        if mode == "any":
+            out = torch.empty((n,), dtype=torch.uint8, device=dev)
+            self.ctx._check(self.overlapTrianglesDevice(tptr, n, _lib.TRIS_ANY, out.data_ptr() if n else 0, flags=flags,
+                                                        counters=cnt))
+            res = {"any": out.view(torch.bool)}
+        else:
+            count = torch.empty((n,), dtype=torch.int32, device=dev)
+            if mode == "count":
+                self.ctx._check(self.overlapTrianglesDevice(tptr, n, _lib.TRIS_COUNT, count.data_ptr() if n else 0,
+                                                            flags=flags, counters=cnt))
+                res = {"count": count}
+            else:
+                self.ctx._check(self.overlapTrianglesDevice(tptr, n, _lib.TRIS_COUNT, count.data_ptr() if n else 0,
+                                                            flags=flags))
+                if not on_device:
+                    self.ctx.sync()  # the counts, before torch's stream reads them
+                offsets = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
+                torch.cumsum(count, 0, dtype=torch.int32, out=offsets[1:])
+                total = int(offsets[-1].item())  # the one read; it also puts the offsets before the list pass
+                ids = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)  # never a null pointer
+                self.ctx._check(self.overlapTrianglesDevice(tptr, n, _lib.TRIS_LIST, 0, offsets.data_ptr(),
+                                                            ids.data_ptr(), flags=flags, counters=cnt))
+                res = {"count": count, "offsets": offsets, "ids": ids[:total]}
+        self._tris_keep = rec  # until the next query: the kernel may not have read them yet
+        if not on_device:
+            self.ctx.sync()
+            res = {k: (v.cpu().numpy() if k == "any" else v.cpu().numpy().view(np.uint32)) for k, v in res.items()}
+        if counters:
+            res["counters"] = cnt
+        return res
+
+    def selfIntersections(self, shared=None, indices=None):
+        """The pairs of scene triangles that intersect each other: an (m, 2) int64 numpy array of global
+        triangle ids, i < j per row, rows in ascending order.
+
+        The scene is queried with its own triangles in list mode, each reconstructed from export()'s records
+        (v0, v0 + e1, v0 + e2: the same bits the scene side of the test uses) and carrying its own id in pad0
+        under TRIS_PAD_SKIP_TRI. The translated test is not bit-symmetric in its arguments, so a pair is
+        reported when either direction accepts it: the union is the definition.
+
+        Neighbours in a mesh touch by construction. Pairs for which shared(i, j) is true are left out.
+        shared=None: "the two triangles belong to the same scene entry and have a vertex index in common",
+        from hitAttributes(ATTR_MESH_FACE) and the entries' index arrays. IScene does not keep index arrays,
+        so the caller passes them: indices is one array of 3 * faces indices per scene entry, in entry order
+        (an instance entry: its mesh's). A callable `shared` needs no indices; it is called once per
+        intersecting pair with (i, j), i < j. Waits for the result."""
+        if shared is None and indices is None:
+            raise BeamError(ERROR_INVALID_PARAMETER,
+                            "selfIntersections: pass the entries' index arrays (indices=[...]) or a shared(i, j)")
+        _, tris, _, _ = self.export()
+        n = tris.shape[0]
+        if n == 0:
+            return np.zeros((0, 2), np.int64)
+        tf, gid = tris.view(np.float32), tris[:, 3]
+        v0 = tf[:, 0:3]
+        q = np.zeros((n, 3, 3), np.float32)
+        q[gid] = np.stack([v0, v0 + tf[:, 4:7], v0 + tf[:, 8:11]], axis=1)
+        res = self.overlapTriangles(q, mode="list", skip_tri=np.arange(n, dtype=np.uint32))
+        i = np.repeat(np.arange(n, dtype=np.int64), res["count"].astype(np.int64))
+        j = res["ids"].astype(np.int64)
+        pairs = np.unique(np.stack([np.minimum(i, j), np.maximum(i, j)], axis=1), axis=0).reshape(-1, 2)
+        if pairs.shape[0] == 0:
+            return pairs
+        if shared is not None:
+            keep = np.array([not shared(int(a), int(b)) for a, b in pairs], bool)
+            return pairs[keep]
+        hits = np.zeros((n, 4), np.float32)
+        hits.view(np.uint32)[:, 3] = np.arange(n, dtype=np.uint32)
+        (face,) = self.hitAttributes(hits, [(ATTR_MESH_FACE, 2)])
+        vidx = np.zeros((n, 3), np.int64)
+        for e, idx in enumerate(indices):
+            mine = face[:, 0] == e
+            vidx[mine] = np.asarray(idx, np.int64).reshape(-1, 3)[face[mine, 1]]
+        a, b = pairs[:, 0], pairs[:, 1]
+        touch = (face[a, 0] == face[b, 0]) & (vidx[a][:, :, None] == vidx[b][:, None, :]).any(axis=(1, 2))
+        return pairs[~touch]
+
     def closestPointsDevice(self, points_ptr: int, n: int, out_ptr: int, counters=None, flags=0) -> int:
         """bm_scene_closest_points on device pointers (n bm_point records of 16 bytes in, n bm_hit records of
         16 bytes out, both 16-byte aligned); returns the error code. Asynchronous on the context stream unless

@@ -2227,6 +2227,74 @@ int32_t bm_scene_overlap_boxes_counters(bm_scene* s, const bm_box* boxes_dev, ui
     return boxes_impl(s, boxes_dev, n, mode, flags, out_dev, offsets_dev, ids_dev, out);
 }
 
+// ---- triangle overlap queries (bm_tris.hip) ------------------------------------------------------
+// boxes_impl's path and order of checks; the one flag travels in q_flags.
+static int32_t tris_impl(bm_scene* s, const bm_tri* tris, uint32_t n, uint32_t mode, uint32_t flags, void* out,
+                         const uint32_t* offsets, uint32_t* ids, uint64_t* counters) {
+    if (!s) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = s->ctx;
+    const std::string who = "overlap_triangles: ";
+    const bool list = mode == BM_TRIS_LIST;
+    if (n && (!tris || (!list && !out) || (list && (!offsets || !ids))))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "null triangle, result, offset or id pointer");
+    if ((reinterpret_cast<uintptr_t>(tris) & 15u) ||
+        (list && ((reinterpret_cast<uintptr_t>(offsets) | reinterpret_cast<uintptr_t>(ids)) & 3u)) ||
+        (mode != BM_TRIS_ANY && (reinterpret_cast<uintptr_t>(out) & 3u)))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER,
+                    who + "the triangle pointer must be 16-byte aligned, count, offset and id pointers 4-byte");
+    if (mode > BM_TRIS_LIST || (flags & ~BM_TRIS_PAD_SKIP_TRI))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "unknown mode or flag bits");
+    if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
+    if (s->kd || s->hash || s->width != 4)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    if (counters) std::fill(counters, counters + 4, uint64_t(0));
+    if (n == 0) return BM_ERROR_ALL_FINE;
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    bm::TraceParams p{};
+    p.nodes = s->records.as<const uint4>();
+    p.tris = s->tris.as<const float4>();
+    p.num_tris = s->n;
+    p.variant = bm::TRACE_QUAD;
+    p.bvh_width = 4;
+    p.prio_after = ctx->prio_after;
+    p.prio_level = ctx->prio_level;
+    p.q_rays = reinterpret_cast<const float4*>(tris);
+    p.q_out = out;
+    p.q_n = n;
+    p.q_flags = flags;
+    p.q_ent = list ? offsets : nullptr;  // launch_overlap_triangles: the segment offsets and the ids
+    p.q_counts = list ? ids : nullptr;
+    if (const int32_t e = reserve_overflow(ctx, nullptr, st, p)) return e;
+    if (counters) {
+        if (!ctx->rays_counters) BM_HIP(ctx, hipMalloc(&ctx->rays_counters, 4 * sizeof(unsigned long long)));
+        BM_HIP(ctx, hipMemsetAsync(ctx->rays_counters, 0, 4 * sizeof(unsigned long long), st));
+        p.counters = ctx->rays_counters;
+    }
+    BM_HIP(ctx, bm::launch_overlap_triangles(p, mode, counters != nullptr, st));
+    if (counters) {
+        unsigned long long h[4];
+        BM_HIP(ctx, hipMemcpyAsync(h, ctx->rays_counters, sizeof(h), hipMemcpyDeviceToHost, st));
+        BM_HIP(ctx, hipStreamSynchronize(st));
+        std::copy(h, h + 4, counters);
+    }
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_overlap_triangles(bm_scene* s, const bm_tri* tris_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                                   void* out_dev, const uint32_t* offsets_dev, uint32_t* ids_dev) {
+    return tris_impl(s, tris_dev, n, mode, flags, out_dev, offsets_dev, ids_dev, nullptr);
+}
+
+int32_t bm_scene_overlap_triangles_counters(bm_scene* s, const bm_tri* tris_dev, uint32_t n, uint32_t mode,
+                                            uint32_t flags, void* out_dev, const uint32_t* offsets_dev,
+                                            uint32_t* ids_dev, uint64_t out[4]) {
+    if (!out) return BM_ERROR_INVALID_PARAMETER;
+    return tris_impl(s, tris_dev, n, mode, flags, out_dev, offsets_dev, ids_dev, out);
+}
+
 // ---- hit attributes (bm_attrs.hip) ---------------------------------------------------------------
 int32_t bm_scene_hit_attributes(bm_scene* s, const bm_hit* hits_dev, uint32_t n, const bm_attr_req* reqs,
                                 uint32_t num_reqs) {

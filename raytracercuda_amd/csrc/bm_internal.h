@@ -252,6 +252,10 @@ hipError_t launch_closest_points_multi(const TraceParams& p, bool count_all, boo
 // where p.q_out is not null, the counts there. count: into p.counters[0..3] (node records, triangle tests,
 // the sum of the counts, the deepest stack held).
 hipError_t launch_overlap_boxes(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
+// Triangle overlap query (bm_tris.hip): the triangles tri_tri accepts for each of p.q_n query triangles, three
+// float4 (v0, pad0) (v1, pad1) (v2, pad2) each in p.q_rays; p.q_flags the call's flags (BM_TRIS_PAD_SKIP_TRI:
+// pad0 is an id never reported). Modes, outputs and counters as launch_overlap_boxes, under the same names.
+hipError_t launch_overlap_triangles(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
 // ---- hit attributes (bm_attrs.hip): vertex slots interpolated at the hits of a ray query ------------
 // One entry per scene mesh, in scene order: every slot's device buffer (null: the mesh has none), so the
 // table depends on the meshes alone and not on what a call requests.
