@@ -282,6 +282,13 @@ class IScene {
                            uint32_t* deviceCounts = nullptr) {
         return (u32)bm_scene_closest_points_multi(h_, devicePoints, n, k, flags, deviceHits, deviceCounts);
     }
+    // Extension: the first contact of each of n swept spheres in device memory (bm_scene_sweep_spheres;
+    // asynchronous on the context stream). mode BM_SWEEP_CLOSEST: deviceOut is bm_hit[n] (t along dir, the
+    // contact point's barycentrics and triangle; hitAttributes gives the contact position); BM_SWEEP_ANY:
+    // uint8_t[n], whether the sphere touches anything within tmax.
+    u32 sweepSpheres(const bm_sweep* deviceSweeps, u32 n, u32 mode, void* deviceOut) {
+        return (u32)bm_scene_sweep_spheres(h_, deviceSweeps, n, mode, 0, deviceOut);
+    }
     // Extension: the triangles that intersect each of n axis-aligned boxes in device memory
     // (bm_scene_overlap_boxes; asynchronous on the context stream). mode BM_BOXES_COUNT: deviceOut is
     // uint32_t[n]; BM_BOXES_ANY: uint8_t[n]; BM_BOXES_LIST: the ids go to deviceIds at the segments of

@@ -542,6 +542,87 @@ int32_t bm_scene_closest_points_multi_counters(bm_scene* s, const bm_point* poin
                                                uint32_t flags, bm_hit* hits_dev, uint32_t* counts_dev,
                                                uint64_t out[4]);
 
+/* ---- sphere-cast queries: the first contact of a swept sphere per ray ---------------------------
+ * How far can a sphere of radius r travel along a direction before it touches the mesh, and where does it
+ * touch: camera collision, character and projectile controllers, thick line of sight, clearance along a
+ * tool path, continuous collision of particles. A few ordinary rays miss edges and vertices between them
+ * and tunnel through thin features; a radius query answers only the stationary case.
+ * sweeps_dev and out_dev are device pointers on the context's device, 16-byte aligned. The work is
+ * enqueued on the context stream and the call returns without waiting; bm_sync waits. On a multi-device
+ * context the query runs on the root device alone.
+ * A sweep is a bm_ray whose pad word is the radius. The sphere's centre moves as c(t) = origin + t*dir for
+ *   0 <= t <= tmax; dir need not be normalised (t is in units of dir), tmax = +inf means unbounded.
+ * BM_SWEEP_CLOSEST: out_dev is bm_hit[n]. The result is the lexicographic minimum of (t_g, g) over ALL
+ *   triangles g of the scene for which the triangle function below returns a t_g with 0 <= t_g <= tmax
+ *   and t_g <= FLT_MAX: equal t resolves to the lowest id. u and v are the barycentrics of the contact
+ *   point on the triangle in the hit-attribute convention (the point is v0*(1-(u+v)) + v1*u + v2*v). A
+ *   sphere that already touches or overlaps triangle g at the start has t_g = 0 with the (u, v) of the
+ *   closest-point function at the origin. Without such a triangle, over an empty scene and for an invalid
+ *   sweep the record is the ray query's miss: t = +inf, u = v = 0, tri_id = BM_NO_TRIANGLE. The record
+ *   feeds bm_scene_hit_attributes as it is: BM_VERTEX_DATA_POSITION is then the contact point, and
+ *   c(t) - contact is the sphere's contact normal.
+ * BM_SWEEP_ANY: out_dev is uint8_t[n]: 1 when any triangle has such a t_g, else 0; the traversal stops at
+ *   the first one. tmax is honoured here (unlike BM_RAYS_ANY_HIT, whose segment is 0 < s < 1 whatever
+ *   tmax says).
+ * Invalid sweeps (a non-finite origin or direction component; an all-zero direction; tmax NaN or negative
+ *   — tmax = 0 is valid and asks only about the start; a radius that is NaN, infinite or <= 0) are not
+ *   traversed: the miss record, or 0.
+ * The triangle function of o = origin, d = dir, r = radius, tl = min(tmax, FLT_MAX) and the triangle's
+ *   v0, e1 = v1 - v0, e2 = v2 - v0 (each one float32 subtraction per component), in float32, one rounding
+ *   per operation in the order written, never contracted; dot and cross as stated at the multi-hit
+ *   queries; divisions and sqrtf correctly rounded; a comparison with NaN is false:
+ *     start:  dd0, u0, v0 = the closest-point section's function of o;   rr = r*r
+ *             dd0 <= rr  ->  t = 0, u = u0, v = v0
+ *     ap = o - v0        dd = dot(d,d)
+ *     1. face:   n = cross(e1,e2)   nn = dot(n,n)   h = dot(n,ap)   nd = dot(n,d)   ln = sqrtf(nn)
+ *                hs = |h|   nds = h >= 0 ? nd : -nd      t = (hs - r*ln) / (-nds)
+ *                w = ap + d*t   per component: ap.x + d.x*t
+ *                u = dot(n, cross(w,e2)) / nn      v = dot(n, cross(e1,w)) / nn
+ *                accepted: nds < 0 && u >= 0 && v >= 0 && u + v <= 1 && t >= 0 && t <= tl
+ *     edge(m, E, md, mm):  EE = dot(E,E)   Ed = dot(E,d)   Em = dot(E,m)
+ *                qa = EE*dd - Ed*Ed    qb = EE*md - Ed*Em    qc = EE*(mm - rr) - Em*Em
+ *                disc = qb*qb - qa*qc    t = (-qb - sqrtf(disc)) / qa    s = (Em + t*Ed) / EE
+ *                accepted: disc >= 0 && qa > 0 && s >= 0 && s <= 1 && t >= 0 && t <= tl
+ *     vertex(md, mm):      disc = md*md - dd*(mm - rr)    t = (-md - sqrtf(disc)) / dd
+ *                accepted: disc >= 0 && dd > 0 && t >= 0 && t <= tl
+ *     md0 = dot(ap,d)  mm0 = dot(ap,ap)   m1 = ap - e1  md1 = dot(m1,d)  mm1 = dot(m1,m1)
+ *     m2 = ap - e2  md2 = dot(m2,d)  mm2 = dot(m2,m2)
+ *     2. edge(ap, e1, md0, mm0)       -> u = s, v = 0
+ *     3. edge(ap, e2, md0, mm0)       -> u = 0, v = s
+ *     4. edge(m1, e2 - e1, md1, mm1)  -> u = 1 - s, v = s
+ *     5. vertex(md0, mm0) -> u = 0, v = 0    6. vertex(md1, mm1) -> u = 1, v = 0
+ *     7. vertex(md2, mm2) -> u = 0, v = 1
+ *   Without a start, t_g is the smallest t of the accepted candidates, the earlier one in this list on
+ *   equal t; with none accepted the triangle has no t_g. A NaN is never accepted.
+ * Resolution: the roots cancel in float32 when the origin is far away compared with r (mm - rr against
+ *   mm, and the discriminant's two products). With S the largest |origin - vertex| involved, the centre
+ *   at the reported t lies within about 2^-10 * S of distance r from the triangle, and a radius below
+ *   about 2^-11 * S is not resolved: such a sphere is swept as if its radius were anything up to that.
+ *   The traversal's pruning margin is sized from the same figure, so what it returns is still the
+ *   function's minimum over all triangles, bit for bit. Origins within BM_ENVELOPE_EXTENTS of the scene,
+ *   as at bm_camera_trace.
+ * flags: none defined yet, pass 0 (the pad word is taken: the ray query's filters do not apply). Sweeps are
+ * taken in the order given, 16 consecutive sweeps per wave.
+ * BM_ERROR_INVALID_PARAMETER: a null handle, a null pointer with n > 0, a misaligned pointer, an unknown
+ * mode or any flag bit, a scene of a reference-mode, BVH2 or BVH8 context. BM_ERROR_NOT_BUILT: the scene
+ * has no current build. n = 0 succeeds without a launch. */
+typedef struct bm_sweep {
+    float origin[3];
+    float tmax;
+    float dir[3];
+    float radius;
+} bm_sweep; /* 32 B, bm_ray's layout with pad = radius */
+#define BM_SWEEP_CLOSEST 0u
+#define BM_SWEEP_ANY 1u
+int32_t bm_scene_sweep_spheres(bm_scene* s, const bm_sweep* sweeps_dev, uint32_t n, uint32_t mode,
+                               uint32_t flags, void* out_dev);
+/* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle evaluations,
+ * out[2] sweeps with a result (BM_SWEEP_ANY: sweeps that touch), out[3] the largest number of stack
+ * entries any sweep held at once (above 24 the traversal used the global overflow area); invalid sweeps
+ * count nothing. Results are written exactly as bm_scene_sweep_spheres writes them. Synchronous. */
+int32_t bm_scene_sweep_spheres_counters(bm_scene* s, const bm_sweep* sweeps_dev, uint32_t n, uint32_t mode,
+                                        uint32_t flags, void* out_dev, uint64_t out[4]);
+
 /* ---- box overlap queries: the triangles that intersect each box of a batch ---------------------
  * The third family beside rays and points: volumes. For axis-aligned box i: which triangles of the
  * scene touch it — voxelising a mesh into an occupancy grid, selecting a region, the broad phase of

@@ -105,6 +105,14 @@ class Point(C.Structure):
     _fields_ = [("p", C.c_float * 3), ("rmax", C.c_float)]
 
 
+class Sweep(C.Structure):
+    """bm_sweep: one swept sphere of bm_scene_sweep_spheres (32 bytes: bm_ray's layout with pad = radius)."""
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("dir", C.c_float * 3), ("radius", C.c_float)]
+
+
+SWEEP_CLOSEST, SWEEP_ANY = 0, 1  # its modes
+
+
 class Box(C.Structure):
     """bm_box: one axis-aligned box of bm_scene_overlap_boxes (32 bytes)."""
     _fields_ = [("center", C.c_float * 3), ("pad0", C.c_uint32), ("half", C.c_float * 3), ("pad1", C.c_uint32)]
@@ -205,6 +213,8 @@ SIGNATURES = {
     "bm_scene_closest_points_counters": (_I, [_P, _P, _U, _U, _P, _U64P]),
     "bm_scene_closest_points_multi": (_I, [_P, _P, _U, _U, _U, _P, _P]),
     "bm_scene_closest_points_multi_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _U64P]),
+    "bm_scene_sweep_spheres": (_I, [_P, _P, _U, _U, _U, _P]),
+    "bm_scene_sweep_spheres_counters": (_I, [_P, _P, _U, _U, _U, _P, _U64P]),
     "bm_scene_overlap_boxes": (_I, [_P, _P, _U, _U, _U, _P, _P, _P]),
     "bm_scene_overlap_boxes_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _U64P]),
     "bm_scene_overlap_triangles": (_I, [_P, _P, _U, _U, _U, _P, _P, _P]),

@@ -963,6 +963,88 @@ class IScene:
             res["counters"] = cnt
         return res
 
+    def sweepSpheresDevice(self, sweeps, n: int, out, mode: int = _lib.SWEEP_CLOSEST, counters=None, flags=0) -> int:
+        """bm_scene_sweep_spheres on the device: `sweeps` is n bm_sweep records of 32 bytes (origin, tmax, dir,
+        radius), `out` n bm_hit records of 16 bytes (SWEEP_CLOSEST) or n bytes (SWEEP_ANY), each a raw device
+        pointer or a torch tensor on the context's device, 16-byte aligned; returns the error code. Asynchronous
+        on the context stream unless `counters` (a uint64[4] numpy array to fill) is given. flags: none defined."""
+        sp = C.c_void_p((sweeps.data_ptr() if hasattr(sweeps, "data_ptr") else sweeps) or None)
+        op = C.c_void_p((out.data_ptr() if hasattr(out, "data_ptr") else out) or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_sweep_spheres(self.h, sp, n, mode, flags, op)
+        return self.ctx.lib.bm_scene_sweep_spheres_counters(self.h, sp, n, mode, flags, op,
+                                                            counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def sweepSpheres(self, origins, dirs=None, radii=None, tmax=float("inf"), any: bool = False,
+                     counters: bool = False):
+        """The first contact of n swept spheres (bm_scene_sweep_spheres): the centre moves as origin + t * dir
+        for 0 <= t <= tmax (dir need not be normalised); t is where the sphere first touches the scene, u, v
+        the barycentrics of the contact point and tri_id its triangle; a sphere that touches at the start has
+        t = 0, one that never touches the miss record (t = inf, tri_id = NO_TRIANGLE). radii and tmax: a scalar
+        or n values. any=True: one flag per sweep, whether it touches anything within tmax.
+
+        numpy (n,3) float32 origins and dirs: packs, uploads, queries and waits; returns numpy arrays
+        {"t", "u", "v", "tri_id"}, or {"any"} (bool).
+        torch tensors on the context's device — origins and dirs (n,3) with radii and tmax scalars or (n,)
+        tensors, or one packed (n,8) float32 tensor of bm_sweep records as `origins` alone: everything stays on
+        the device and nothing waits. Returns {"hits": (n,4) float32, "t", "u", "v", "tri_id"} with the views
+        traceRays returns, or {"any": (n,) bool}; "hits" goes straight into hitAttributes, where
+        VERTEX_DATA_POSITION is the contact point. Make the context on torch's stream, as for traceRays.
+        counters=True adds "counters": [node records, triangle evaluations, sweeps with a result, deepest
+        stack] (waits)."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        on_device = isinstance(origins, torch.Tensor)
+        if on_device:
+            if origins.dim() == 2 and origins.shape[1] == 8 and dirs is None and radii is None:
+                rec = origins
+            elif origins.dim() == 2 and origins.shape[1] == 3 and dirs is not None and radii is not None:
+                rec = torch.empty((origins.shape[0], 8), dtype=torch.float32, device=origins.device)
+                rec[:, 0:3] = origins
+                rec[:, 3] = tmax
+                rec[:, 4:7] = dirs
+                rec[:, 7] = radii
+            else:
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                "sweepSpheres: origins and dirs are (n, 3) with radii, or one packed (n, 8), float32")
+            if rec.device != dev or rec.dtype != torch.float32 or not rec.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"sweepSpheres: sweeps must be contiguous float32 on {dev} (the context's device)")
+        else:
+            if dirs is None or radii is None:
+                raise BeamError(ERROR_INVALID_PARAMETER, "sweepSpheres: origins, dirs and radii are required")
+            o = _f32(origins).reshape(-1, 3)
+            packed = np.zeros((o.shape[0], 8), np.float32)
+            packed[:, 0:3] = o
+            packed[:, 3] = tmax
+            packed[:, 4:7] = _f32(dirs).reshape(-1, 3)
+            packed[:, 7] = radii
+            rec = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = rec.shape[0]
+        # rows of 16 bytes either way: an empty tensor's pointer is not passed on
+        out = torch.empty((n,), dtype=torch.uint8, device=dev) if any else torch.empty((n, 4), dtype=torch.float32,
+                                                                                       device=dev)
+        cnt = np.zeros(4, np.uint64) if counters else None
+        self.ctx._check(self.sweepSpheresDevice(rec.data_ptr() if n else 0, n, out.data_ptr() if n else 0,
+                                                _lib.SWEEP_ANY if any else _lib.SWEEP_CLOSEST, cnt))
+        self._sweeps_keep = rec  # until the next query: the kernel may not have read them yet
+        if any:
+            res = {"any": out.view(torch.bool)}
+        else:
+            res = {"hits": out, "t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "tri_id": out.view(torch.int32)[:, 3]}
+        if not on_device:
+            self.ctx.sync()
+            if any:
+                res = {"any": out.cpu().numpy().astype(bool)}
+            else:
+                h = out.cpu().numpy()
+                res = {"t": h[:, 0].copy(), "u": h[:, 1].copy(), "v": h[:, 2].copy(),
+                       "tri_id": h.view(np.uint32)[:, 3].copy()}
+        if counters:
+            res["counters"] = cnt
+        return res
+
     def hitAttributesDevice(self, hits_ptr: int, n: int, requests) -> int:
         """bm_scene_hit_attributes on device pointers: n bm_hit records of 16 bytes in, and per request
         (slot, components, flags, out_ptr[, pad]) n rows of `components` 4-byte words out, every pointer

@@ -15,9 +15,9 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libbeam_hip.so")
 SOURCES = ["bm_api.cpp", "bm_obj.cpp", "bm_rccl.cpp", "bm_build.hip", "bm_trace.hip", "bm_trace_ab.hip", "bm_kd.hip",
            "bm_gather.hip", "bm_rays.hip", "bm_points.hip", "bm_attrs.hip", "bm_xform.hip", "bm_multihit.hip",
-           "bm_points_multi.hip", "bm_boxes.hip", "bm_tris.hip"]  # bm_trace_ab.hip is empty unless an A/B build defines BM_TRACE_AB=1
+           "bm_points_multi.hip", "bm_boxes.hip", "bm_tris.hip", "bm_sweep.hip"]  # bm_trace_ab.hip is empty unless an A/B build defines BM_TRACE_AB=1
 HEADERS = ["bm_common.h", "bm_internal.h", "bm_bdiag.h", "bm_sort.h", "bm_trace_dev.h", "bm_trace_lanes.h",
-           "bm_trace_quad.h", "bm_trace_packet.h", "bm_query_dev.h", "bm_sat_dev.h", "bm_tritri_dev.h",
+           "bm_trace_quad.h", "bm_trace_packet.h", "bm_query_dev.h", "bm_sat_dev.h", "bm_tritri_dev.h", "bm_sweep_dev.h",
            os.path.join("..", "..", "include", "beam_c.h")]
 ARCH = os.environ.get("BM_OFFLOAD_ARCH", "gfx950")
 
@@ -25,9 +25,10 @@ ARCH = os.environ.get("BM_OFFLOAD_ARCH", "gfx950")
 # into v_pk_* pairs whose operand shuffles (v_mov) cost more than the pairing saved.
 # bm_xform.hip likewise: it re-cut a lane's three aligned 16-byte loads into 8 + 16 + 8 + 16 bytes (the middle
 # ones off their 16-byte boundary) to feed v_pk_* pairs. bm_tris.hip: packing the seventeen axes of the
-# triangle/triangle test took 240 VGPRs against 96 and spilled at every occupancy.
+# triangle/triangle test took 240 VGPRs against 96 and spilled at every occupancy. bm_sweep.hip:
+# packing the seven candidates of the swept-sphere function took 114 VGPRs against 78.
 SOURCE_FLAGS = {"bm_kd.hip": ["-fno-slp-vectorize"], "bm_xform.hip": ["-fno-slp-vectorize"],
-                "bm_tris.hip": ["-fno-slp-vectorize"]}
+                "bm_tris.hip": ["-fno-slp-vectorize"], "bm_sweep.hip": ["-fno-slp-vectorize"]}
 
 FP_FLAGS = [
     "-ffp-contract=off",

@@ -2004,22 +2004,27 @@ static int32_t filter_setup(bm_scene* s, uint32_t flags, hipStream_t st, bm::Tra
     return BM_ERROR_ALL_FINE;
 }
 
-static int32_t query_impl(bm_scene* s, bool points, const void* in, uint32_t n, uint32_t mode, uint32_t flags,
+enum QueryKernel { QUERY_RAYS, QUERY_POINTS, QUERY_SWEEPS };  // which kernel query_impl's path ends in
+
+static int32_t query_impl(bm_scene* s, QueryKernel kernel, const void* in, uint32_t n, uint32_t mode, uint32_t flags,
                           void* out, uint64_t* counters) {
     if (!s) return BM_ERROR_INVALID_PARAMETER;
     bm_context* ctx = s->ctx;
-    const std::string who = points ? "closest_points: " : "trace_rays: ";
+    const bool rays = kernel == QUERY_RAYS;
+    const std::string who = kernel == QUERY_POINTS ? "closest_points: " : rays ? "trace_rays: " : "sweep_spheres: ";
     if (n && (!in || !out)) return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "null input or result pointer");
     if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "input and result pointers must be 16-byte aligned");
-    if ((!points && mode > BM_RAYS_ANY_HIT) || (points ? flags != 0 : !filter_flags_valid(flags)))  // points: no flag bits
+    static_assert(BM_SWEEP_ANY == BM_RAYS_ANY_HIT, "one mode check serves rays and sweeps");
+    if ((kernel != QUERY_POINTS && mode > BM_RAYS_ANY_HIT) ||
+        (rays ? !filter_flags_valid(flags) : flags != 0))  // points and sweeps: no flag bits
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "unknown mode or flag bits");
     if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
     if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
     if (s->kd || s->hash || s->width != 4)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
-    const int words = points ? 4 : 3;
+    const int words = rays ? 3 : 4;
     if (counters) std::fill(counters, counters + words, uint64_t(0));
     if (n == 0) return BM_ERROR_ALL_FINE;
     BM_HIP(ctx, hipSetDevice(ctx->device));
@@ -2035,7 +2040,7 @@ static int32_t query_impl(bm_scene* s, bool points, const void* in, uint32_t n, 
     p.q_rays = reinterpret_cast<const float4*>(in);
     p.q_out = out;
     p.q_n = n;
-    if (!points)
+    if (rays)
         if (const int32_t e = filter_setup(s, flags, st, p)) return e;
     if (const int32_t e = reserve_overflow(ctx, nullptr, st, p)) return e;
     if (counters) {
@@ -2043,8 +2048,9 @@ static int32_t query_impl(bm_scene* s, bool points, const void* in, uint32_t n, 
         BM_HIP(ctx, hipMemsetAsync(ctx->rays_counters, 0, 4 * sizeof(unsigned long long), st));
         p.counters = ctx->rays_counters;
     }
-    BM_HIP(ctx, points ? bm::launch_closest_points(p, counters != nullptr, st)
-                       : bm::launch_query_rays(p, mode, counters != nullptr, st));
+    BM_HIP(ctx, kernel == QUERY_POINTS ? bm::launch_closest_points(p, counters != nullptr, st)
+                : rays                 ? bm::launch_query_rays(p, mode, counters != nullptr, st)
+                                       : bm::launch_sweep_spheres(p, mode, counters != nullptr, st));
     if (counters) {
         unsigned long long h[4];
         BM_HIP(ctx, hipMemcpyAsync(h, ctx->rays_counters, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -2056,23 +2062,34 @@ static int32_t query_impl(bm_scene* s, bool points, const void* in, uint32_t n, 
 
 int32_t bm_scene_trace_rays(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode, uint32_t flags,
                             void* out_dev) {
-    return query_impl(s, false, rays_dev, n, mode, flags, out_dev, nullptr);
+    return query_impl(s, QUERY_RAYS, rays_dev, n, mode, flags, out_dev, nullptr);
 }
 
 int32_t bm_scene_trace_rays_counters(bm_scene* s, const bm_ray* rays_dev, uint32_t n, uint32_t mode, uint32_t flags,
                                      void* out_dev, uint64_t out[3]) {
     if (!out) return BM_ERROR_INVALID_PARAMETER;
-    return query_impl(s, false, rays_dev, n, mode, flags, out_dev, out);
+    return query_impl(s, QUERY_RAYS, rays_dev, n, mode, flags, out_dev, out);
 }
 
 int32_t bm_scene_closest_points(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t flags, bm_hit* out_dev) {
-    return query_impl(s, true, points_dev, n, 0, flags, out_dev, nullptr);
+    return query_impl(s, QUERY_POINTS, points_dev, n, 0, flags, out_dev, nullptr);
 }
 
 int32_t bm_scene_closest_points_counters(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t flags,
                                          bm_hit* out_dev, uint64_t out[4]) {
     if (!out) return BM_ERROR_INVALID_PARAMETER;
-    return query_impl(s, true, points_dev, n, 0, flags, out_dev, out);
+    return query_impl(s, QUERY_POINTS, points_dev, n, 0, flags, out_dev, out);
+}
+
+int32_t bm_scene_sweep_spheres(bm_scene* s, const bm_sweep* sweeps_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                               void* out_dev) {
+    return query_impl(s, QUERY_SWEEPS, sweeps_dev, n, mode, flags, out_dev, nullptr);
+}
+
+int32_t bm_scene_sweep_spheres_counters(bm_scene* s, const bm_sweep* sweeps_dev, uint32_t n, uint32_t mode,
+                                        uint32_t flags, void* out_dev, uint64_t out[4]) {
+    if (!out) return BM_ERROR_INVALID_PARAMETER;
+    return query_impl(s, QUERY_SWEEPS, sweeps_dev, n, mode, flags, out_dev, out);
 }
 
 // ---- multi-result queries: rays (bm_multihit.hip) and points (bm_points_multi.hip) ---------------

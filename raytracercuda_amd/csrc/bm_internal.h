@@ -256,6 +256,11 @@ hipError_t launch_overlap_boxes(const TraceParams& p, uint32_t mode, bool count,
 // float4 (v0, pad0) (v1, pad1) (v2, pad2) each in p.q_rays; p.q_flags the call's flags (BM_TRIS_PAD_SKIP_TRI:
 // pad0 is an id never reported). Modes, outputs and counters as launch_overlap_boxes, under the same names.
 hipError_t launch_overlap_triangles(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
+// Sphere-cast query (bm_sweep.hip): the first contact of each of p.q_n swept spheres, two float4 (origin, tmax)
+// (dir, radius) each in p.q_rays; BM_SWEEP_CLOSEST: one bm_hit each into p.q_out, BM_SWEEP_ANY: one byte. Set
+// up as for launch_closest_points. count: into p.counters[0..3] (node records, triangle evaluations, sweeps
+// with a result, the deepest stack held).
+hipError_t launch_sweep_spheres(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
 // ---- hit attributes (bm_attrs.hip): vertex slots interpolated at the hits of a ray query ------------
 // One entry per scene mesh, in scene order: every slot's device buffer (null: the mesh has none), so the
 // table depends on the meshes alone and not on what a call requests.
