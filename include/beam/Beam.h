@@ -214,6 +214,18 @@ class IMesh {
         (void)asyncCopy;
         return (u32)bm_mesh_set_indices(h_, indices, numIndices);
     }
+    // Device-side deformation (beam_c.h, "device-side mesh deformation"): vertex data from device memory and a
+    // slot's read-back, both enqueued on the context stream without a host wait, and smooth vertex normals
+    // recomputed from the positions and indices.
+    u32 setVertexDataDevice(const float* verticesDev, u32 numVertices, u32 numComponents, u32 slotId) {
+        return (u32)bm_mesh_set_vertex_data_device(h_, verticesDev, numVertices, numComponents, slotId);
+    }
+    u32 copyVertexDataDevice(u32 slotId, float* outDev, u32 numVertices, u32 numComponents) const {
+        return (u32)bm_mesh_copy_vertex_data_device(h_, slotId, outDev, numVertices, numComponents);
+    }
+    u32 computeNormals(bool normalize = true) {
+        return (u32)bm_mesh_compute_normals(h_, normalize ? BM_NORMALS_NORMALIZE : 0u);
+    }
     wptr<IScene> scene() const { return {}; }
     bm_mesh* handle() const { return h_; }
 

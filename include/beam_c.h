@@ -246,6 +246,59 @@ int32_t bm_mesh_set_vertex_data(bm_mesh* m, const float* data, uint32_t num_vert
 int32_t bm_mesh_set_indices(bm_mesh* m, const uint32_t* indices, uint32_t num_indices);
 void bm_mesh_destroy(bm_mesh* m);
 
+/* ---- device-side mesh deformation: vertex data from device memory, vertex normals ---------
+ * For meshes whose vertices are computed on the GPU (cloth, soft bodies, skinning, morph targets): the loop
+ * "simulate, upload, refit, query" without a copy to the host and without a host wait. All three calls work
+ * on the context stream; make the context on the stream the simulation runs on (bm_options.stream) and the
+ * stream orders everything.
+ * bm_mesh_set_vertex_data_device: bm_mesh_set_vertex_data with data_dev in device memory of the context's
+ *   device: the same parameter rules, checks and error codes. data_dev must not overlap the slot (the library
+ *   hands out no slot address, so a buffer of the caller's own never does). The copy is enqueued on the context stream and the call returns without waiting, unless the slot has to
+ *   grow (its first upload, or more bytes than any before), which waits as every growing buffer does. Work
+ *   enqueued on the context stream before the call sees the old values, work enqueued after it the new ones:
+ *   bm_scene_hit_attributes reads mesh slots when its kernel runs and follows that order; builds, refits
+ *   and instance transforms read them at build time, so a trace sees new vertices after the next
+ *   bm_scene_refit or bm_scene_build. Traces on a render target's own stream (bm_rt_set_stream) are ordered
+ *   before the write by an event, not by a host wait. Host and device uploads may be mixed on one mesh;
+ *   the host call keeps its synchronous behaviour.
+ * bm_mesh_copy_vertex_data_device: the slot's current contents, copied device to device on the context
+ *   stream into out_dev (num_vertices * num_components floats); no host wait.
+ * bm_mesh_compute_normals: writes the BM_VERTEX_DATA_NORMAL slot (3 components; created when absent, so a
+ *   positions-only mesh can then be built) from the position slot and the indices, on the context stream.
+ *   The first call after a bm_mesh_set_indices builds the mesh's vertex -> corner table and waits on the
+ *   host for that; every later call enqueues one kernel launch and nothing else. The result is defined to
+ *   the bit, in float32 with one rounding per operation and no contraction:
+ *     for vertex v, take the corners c = 3f + k with idx[c] == v in ascending c (a face naming v twice
+ *     contributes twice); with e1 = p[idx[3f+1]] - p[idx[3f]] and e2 = p[idx[3f+2]] - p[idx[3f]] the
+ *     corner's face vector is BM_ATTR_GEOM_NORMAL's,
+ *       (e1.y*e2.z - e2.y*e1.z,  e1.z*e2.x - e2.z*e1.x,  e1.x*e2.y - e2.x*e1.y),
+ *     area-weighted and not normalised; s starts at (0,0,0) and each face vector is added to it component
+ *     by component in that order. With BM_NORMALS_NORMALIZE, d = (s.x*s.x + s.y*s.y) + s.z*s.z and, if
+ *     d > 0, each component is multiplied by 1.f / sqrtf(d) (BM_ATTR_NORMALIZE's arithmetic: a d of +inf
+ *     gives zeros); otherwise s is stored as it is: a vertex without faces, or with degenerate faces only,
+ *     gets zeros, and a NaN stays a NaN.
+ *   No atomic and no launch shape takes part: the result is the same on every grid and every GPU. A mesh
+ *   without indices gets zeros.
+ * Multi-device contexts: every replica of the mesh receives an upload by a peer copy ordered after the root's
+ *   stream, and computes its own normals. There bm_mesh_set_vertex_data_device and bm_mesh_compute_normals
+ *   may wait on the host.
+ * Errors:
+ *   bm_mesh_set_vertex_data_device   BM_ERROR_INVALID_PARAMETER: a null handle or pointer, no vertices, a
+ *                                    slot past BM_VERTEX_DATA_COUNT, components outside 1..4 (positions: 3),
+ *                                    a vertex count other than the mesh's.
+ *   bm_mesh_copy_vertex_data_device  BM_ERROR_INVALID_PARAMETER: a null handle or pointer, a slot past
+ *                                    BM_VERTEX_DATA_COUNT, counts other than the slot's.
+ *                                    BM_ERROR_NO_VERTICES: the slot is empty.
+ *   bm_mesh_compute_normals          BM_ERROR_INVALID_PARAMETER: a null handle, an unknown flag bit, an index
+ *                                    at or past the vertex count. BM_ERROR_NO_VERTICES: no 3-component
+ *                                    position slot. */
+#define BM_NORMALS_NORMALIZE 1u
+int32_t bm_mesh_set_vertex_data_device(bm_mesh* m, const float* data_dev, uint32_t num_vertices,
+                                       uint32_t num_components, uint32_t slot);
+int32_t bm_mesh_copy_vertex_data_device(const bm_mesh* m, uint32_t slot, float* out_dev,
+                                        uint32_t num_vertices, uint32_t num_components);
+int32_t bm_mesh_compute_normals(bm_mesh* m, uint32_t flags);
+
 /* ---- scene: IScene (Beam.h:56-63, Scene.cpp, SceneTree.cpp) ------------------------------ */
 int32_t bm_scene_create(bm_context* ctx, bm_scene** out);
 /* The scene references (does not own) its meshes; keep them alive while it uses them. */
@@ -1079,6 +1132,14 @@ int32_t bm_camera_trace_profile(bm_camera* c, const float* eye3, const float* or
  * Morton keys, perm[num_tris] sorted position -> global triangle id. */
 int32_t bm_scene_export(bm_scene* s, uint32_t* records, uint32_t* tris, uint32_t* keys,
                         uint32_t* perm);
+/* For tests: bm_mesh_compute_normals' kernel over the caller's own device buffers, on the context stream, so
+ * that a test can supply the vertex -> corner table and look behind the last row written. pos_dev: 3 * nv
+ * floats; idx_dev: the indices; table_dev: nv + 1 row offsets, then the corner ids sorted by vertex (every id
+ * below the number of indices, every index below nv: the caller's duty, nothing is checked); nrm_dev receives
+ * 3 * nv floats. flags as bm_mesh_compute_normals. BM_ERROR_INVALID_PARAMETER for a null context or, with
+ * nv > 0, a null pos_dev, table_dev or nrm_dev, and for an unknown flag bit. Asynchronous. */
+int32_t bm_debug_vertex_normals(bm_context* ctx, const float* pos_dev, const uint32_t* idx_dev,
+                                const uint32_t* table_dev, float* nrm_dev, uint32_t nv, uint32_t flags);
 
 #ifdef __cplusplus
 }

@@ -140,6 +140,7 @@ class AttrReq(C.Structure):
 ATTR_GEOM_NORMAL, ATTR_MESH_FACE = 16, 17  # pseudo-slots
 ATTR_NORMALIZE = 1                         # flag
 ATTR_MAX_REQS = 4
+NORMALS_NORMALIZE = 1  # bm_mesh_compute_normals' flag
 
 # bm_context_set_param keys (BM_PARAM_* in include/beam_c.h), by the names beam.Context(params=...) takes
 PARAMS = {"trace_variant": 0, "trace_sched": 1, "trace_scramble": 2, "trace_prio_after": 3, "trace_prio_level": 4,
@@ -179,6 +180,10 @@ SIGNATURES = {
     "bm_mesh_set_vertex_data": (_I, [_P, _FP, _U, _U, _U]),
     "bm_mesh_set_indices": (_I, [_P, _UP, _U]),
     "bm_mesh_destroy": (None, [_P]),
+    "bm_mesh_set_vertex_data_device": (_I, [_P, _P, _U, _U, _U]),
+    "bm_mesh_copy_vertex_data_device": (_I, [_P, _U, _P, _U, _U]),
+    "bm_mesh_compute_normals": (_I, [_P, _U]),
+    "bm_debug_vertex_normals": (_I, [_P, _P, _P, _P, _P, _U, _U]),
     "bm_scene_create": (_I, [_P, C.POINTER(_P)]),
     "bm_scene_add_mesh": (_I, [_P, _P]),
     "bm_scene_remove_mesh": (_I, [_P, _P]),

@@ -29,7 +29,8 @@ from ._lib import (ERROR_ALL_FINE, ERROR_DEVICE, ERROR_GPU_ALLOC_FAIL, ERROR_INV
                    SORT_LSD, SORT_MSD, SORT_MSD_SKEW, SORT_KD_RANKED,
                    VERTEX_DATA_UV1, VERTEX_DATA_UV2, VERTEX_DATA_TANGENT, VERTEX_DATA_BITANGENT, VERTEX_DATA_EXTRA1,
                    VERTEX_DATA_EXTRA2, VERTEX_DATA_EXTRA3, VERTEX_DATA_EXTRA4,
-                   ATTR_GEOM_NORMAL, ATTR_MESH_FACE, ATTR_NORMALIZE, ATTR_MAX_REQS)
+                   ATTR_GEOM_NORMAL, ATTR_MESH_FACE, ATTR_NORMALIZE, ATTR_MAX_REQS,
+                   NORMALS_NORMALIZE)
 
 
 def _f32(a):
@@ -268,16 +269,75 @@ class IMesh:
         h = C.c_void_p()
         ctx._check(ctx.lib.bm_mesh_create(ctx.h, C.byref(h)))
         self.h = h
+        self._slot_comp = {}     # slot -> components, as uploaded (vertexData sizes its tensor by them)
+        self._num_vertices = 0
+        self._upload_keep = None
 
     @staticmethod
     def create(ctx: Context) -> "IMesh":
         return IMesh(ctx)
 
     def setVertexData(self, vertices, numVertices: int, numComponents: int, slotId: int, asyncCopy: bool = False):
+        """A slot's values for every vertex (bm_mesh_set_vertex_data): host values, copied synchronously; returns
+        the error code.
+
+        A torch tensor on the context's device takes the device path (bm_mesh_set_vertex_data_device): the copy
+        is enqueued on the context stream and nothing waits (unless the slot has to grow). The tensor is
+        contiguous float32, shaped (numVertices, numComponents) or flat; anything else about it, and any error
+        of the call, raises BeamError. Make the context on torch's stream
+        (Context(stream=torch.cuda.current_stream().cuda_stream)) so that the simulation that wrote the tensor,
+        this upload, computeNormals, refitGPUScene and the queries after it are ordered; the tensor may then be
+        rewritten right after the call. The two forms may be mixed on one mesh."""
+        import sys
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(vertices, torch.Tensor):
+            t = vertices
+            dev = torch.device("cuda", self.ctx.device)
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"setVertexData: the tensor must be contiguous float32 on {dev} (the context's device)")
+            if tuple(t.shape) not in ((numVertices, numComponents), (numVertices * numComponents,)):
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                "setVertexData: the tensor is (numVertices, numComponents) or flat")
+            self.ctx._check(self.ctx.lib.bm_mesh_set_vertex_data_device(self.h, t.data_ptr(), numVertices,
+                                                                        numComponents, slotId))
+            self._upload_keep = t  # until the next upload: the copy may not have read it yet
+            self._slot_comp[slotId] = numComponents
+            self._num_vertices = numVertices
+            return ERROR_ALL_FINE
         a = _f32(vertices).reshape(-1)
         if a.size < numVertices * numComponents:
             return ERROR_INVALID_PARAMETER
-        return self.ctx.lib.bm_mesh_set_vertex_data(self.h, _fp(a), numVertices, numComponents, slotId)
+        err = self.ctx.lib.bm_mesh_set_vertex_data(self.h, _fp(a), numVertices, numComponents, slotId)
+        if not err:
+            self._slot_comp[slotId] = numComponents
+            self._num_vertices = numVertices
+        return err
+
+    def computeNormals(self, normalize: bool = True) -> None:
+        """bm_mesh_compute_normals: rewrites the NORMAL slot (creating it when absent) from the POSITION slot and
+        the indices, on the context stream: smooth, area-weighted vertex normals, defined to the bit
+        (include/beam_c.h). The first call after setIndices builds the vertex -> corner table and waits; later
+        calls enqueue one launch. With the context on torch's stream the loop setVertexData(tensor),
+        computeNormals(), refitGPUScene(), queries needs no synchronisation."""
+        self.ctx._check(self.ctx.lib.bm_mesh_compute_normals(self.h, NORMALS_NORMALIZE if normalize else 0))
+        self._slot_comp[VERTEX_DATA_NORMAL] = 3
+
+    def vertexData(self, slotId: int):
+        """The slot's current contents as a fresh (numVertices, numComponents) float32 torch tensor on the
+        context's device (bm_mesh_copy_vertex_data_device): a device-to-device copy on the context stream, no
+        host wait. Read it on the context's stream (or after ctx.sync())."""
+        import torch
+        if not 0 <= slotId < VERTEX_DATA_COUNT:
+            raise BeamError(ERROR_INVALID_PARAMETER, "vertexData: unknown slot")
+        comp = self._slot_comp.get(slotId, 0)  # as set through this object
+        if not comp or not self._num_vertices:
+            raise BeamError(ERROR_NO_VERTICES, "vertexData: the slot is empty")
+        dev = torch.device("cuda", self.ctx.device)
+        out = torch.empty((self._num_vertices, comp), dtype=torch.float32, device=dev)
+        self.ctx._check(self.ctx.lib.bm_mesh_copy_vertex_data_device(self.h, slotId, out.data_ptr(),
+                                                                     self._num_vertices, comp))
+        return out
 
     def setIndices(self, indices, numIndices: int, asyncCopy: bool = False):
         a = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)

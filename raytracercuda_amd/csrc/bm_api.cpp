@@ -130,6 +130,12 @@ struct bm_mesh {
     DevBuf slot[BM_VERTEX_DATA_COUNT];
     uint32_t slot_comp[BM_VERTEX_DATA_COUNT] = {};
     DevBuf idx;
+    // bm_mesh_compute_normals (bm_normals.hip): the vertex -> corner table of the current indices, num_vertices + 1
+    // row offsets and then the num_indices corner ids stably sorted by vertex. Built by the first call after a
+    // bm_mesh_set_indices (which only clears corners_valid); each replica keeps its own
+    DevBuf corners;
+    bool corners_valid = false;
+    hipEvent_t upload_ev = nullptr;  // multi-device: a device upload has reached this (root) mesh's stream
 };
 
 struct bm_scene {
@@ -709,6 +715,7 @@ int32_t bm_mesh_set_indices(bm_mesh* m, const uint32_t* indices, uint32_t num_in
     }
     m->num_indices = num_indices;
     m->max_index = mx;
+    m->corners_valid = false;  // the next bm_mesh_compute_normals rebuilds its table
     for (bm_mesh* r : m->rep) {
         const int32_t rc = bm_mesh_set_indices(r, indices, num_indices);
         if (rc) return peer_fail(ctx, r->ctx, rc);
@@ -723,7 +730,140 @@ void bm_mesh_destroy(bm_mesh* m) {
     (void)hipStreamSynchronize(m->ctx->stream);
     for (auto& s : m->slot) s.release();
     m->idx.release();
+    m->corners.release();
+    if (m->upload_ev) (void)hipEventDestroy(m->upload_ev);
     delete m;
+}
+
+// ---- device-side mesh deformation -----------------------------------------------
+// The checks of bm_mesh_set_vertex_data, in its order and with its message.
+static bool vertex_data_args_valid(const bm_mesh* m, const void* data, uint32_t num_vertices, uint32_t num_components,
+                                   uint32_t slot) {
+    return !(!data || num_vertices == 0 || slot >= BM_VERTEX_DATA_COUNT || num_components == 0 || num_components > 4 ||
+             (m->num_vertices != 0 && m->num_vertices != num_vertices) ||
+             (slot == BM_VERTEX_DATA_POSITION && num_components != 3));
+}
+
+// One mesh (the root's or a replica's) takes the slot's new contents from device memory of device src_device,
+// on its own context stream and, when `after` is given, after that event. Every reader of a mesh slot runs on
+// the context stream but the lazy tri_orig rebuild of a multi-device trace, which may run on a render target's
+// own stream: ctx_drain orders the write after it, on the device.
+static int32_t mesh_receive_device(bm_mesh* m, const float* src, int src_device, hipEvent_t after,
+                                   uint32_t num_vertices, uint32_t num_components, uint32_t slot) {
+    bm_context* ctx = m->ctx;
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(float) * (size_t)num_components * num_vertices;
+    BM_HIP(ctx, ctx_drain(ctx));
+    GrowGuard grow{ctx};  // work still queued may read the old slot
+    BM_HIP(ctx, grow.reserve(m->slot[slot], bytes));
+    if (after) BM_HIP(ctx, hipStreamWaitEvent(ctx->stream, after, 0));
+    if (src_device == ctx->device)
+        BM_HIP(ctx, hipMemcpyAsync(m->slot[slot].p, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    else
+        BM_HIP(ctx, hipMemcpyPeerAsync(m->slot[slot].p, ctx->device, src, src_device, bytes, ctx->stream));
+    m->slot_comp[slot] = num_components;
+    m->num_vertices = num_vertices;
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_mesh_set_vertex_data_device(bm_mesh* m, const float* data_dev, uint32_t num_vertices,
+                                       uint32_t num_components, uint32_t slot) {
+    if (!m) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = m->ctx;
+    if (!vertex_data_args_valid(m, data_dev, num_vertices, num_components, slot))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "setVertexData: invalid parameter (Mesh.cpp:32-37)");
+    const int32_t rc0 = mesh_receive_device(m, data_dev, ctx->device, nullptr, num_vertices, num_components, slot);
+    if (rc0 || m->rep.empty()) return rc0;
+    // the replicas read the caller's buffer once the root's stream has reached this call; the caller may
+    // rewrite that buffer in the root's stream order right after it, so the peer copies are waited for here
+    if (!m->upload_ev) BM_HIP(ctx, hipEventCreateWithFlags(&m->upload_ev, hipEventDisableTiming));
+    BM_HIP(ctx, hipEventRecord(m->upload_ev, ctx->stream));
+    for (bm_mesh* r : m->rep) {
+        const int32_t rc = mesh_receive_device(r, data_dev, ctx->device, m->upload_ev, num_vertices, num_components, slot);
+        if (rc) return peer_fail(ctx, r->ctx, rc);
+    }
+    for (bm_mesh* r : m->rep) {
+        BM_HIP(ctx, hipSetDevice(r->ctx->device));
+        BM_HIP(ctx, hipStreamSynchronize(r->ctx->stream));
+    }
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_mesh_copy_vertex_data_device(const bm_mesh* m, uint32_t slot, float* out_dev, uint32_t num_vertices,
+                                        uint32_t num_components) {
+    if (!m) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = m->ctx;
+    if (!out_dev || slot >= BM_VERTEX_DATA_COUNT)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "copyVertexData: null pointer or unknown slot");
+    if (!m->slot[slot].p || !m->slot_comp[slot] || !m->num_vertices)
+        return fail(ctx, BM_ERROR_NO_VERTICES, "copyVertexData: the slot is empty");
+    if (num_vertices != m->num_vertices || num_components != m->slot_comp[slot])
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "copyVertexData: the counts differ from the slot's");
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    BM_HIP(ctx, hipMemcpyAsync(out_dev, m->slot[slot].p, sizeof(float) * (size_t)num_components * num_vertices,
+                               hipMemcpyDeviceToDevice, ctx->stream));
+    return BM_ERROR_ALL_FINE;
+}
+
+// The vertex -> corner table of the mesh's current indices: one read-back of the index buffer, a counting sort
+// on the host (stable by construction: corners are dealt to their vertices' rows in ascending order), one
+// upload. Waits on the host; runs once per bm_mesh_set_indices.
+static int32_t mesh_build_corners(bm_mesh* m) {
+    bm_context* ctx = m->ctx;
+    const uint32_t nv = m->num_vertices, ni = m->num_indices;
+    std::vector<uint32_t> idx(ni), table((size_t)nv + 1 + ni, 0u);
+    if (ni) {
+        BM_HIP(ctx, hipMemcpyAsync(idx.data(), m->idx.p, sizeof(uint32_t) * (size_t)ni, hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        BM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    uint32_t* offsets = table.data();
+    uint32_t* corners = table.data() + nv + 1;
+    for (uint32_t c = 0; c < ni; ++c) {
+        if (idx[c] >= nv) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "index out of range of the mesh's vertices");
+        ++offsets[idx[c] + 1];
+    }
+    for (uint32_t v = 0; v < nv; ++v) offsets[v + 1] += offsets[v];
+    std::vector<uint32_t> cursor(offsets, offsets + nv);
+    for (uint32_t c = 0; c < ni; ++c) corners[cursor[idx[c]]++] = c;
+    GrowGuard grow{ctx};  // an earlier call's kernel still queued may read the old table
+    BM_HIP(ctx, grow.reserve(m->corners, sizeof(uint32_t) * table.size()));
+    BM_HIP(ctx, hipMemcpyAsync(m->corners.p, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice,
+                               ctx->stream));
+    BM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the host image leaves scope
+    m->corners_valid = true;
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_mesh_compute_normals(bm_mesh* m, uint32_t flags) {
+    if (!m) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = m->ctx;
+    if (flags & ~BM_NORMALS_NORMALIZE) return fail(ctx, BM_ERROR_INVALID_PARAMETER, "computeNormals: unknown flag bits");
+    if (!m->slot[BM_VERTEX_DATA_POSITION].p || m->slot_comp[BM_VERTEX_DATA_POSITION] != 3 || !m->num_vertices)
+        return fail(ctx, BM_ERROR_NO_VERTICES, "mesh without a 3-component position slot");
+    if (m->num_indices && (!m->idx.p || m->max_index >= m->num_vertices))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "index out of range of the mesh's vertices");
+    for (bm_mesh* r : m->rep) {  // every replica computes its own, as it transforms its own instances
+        const int32_t rc = bm_mesh_compute_normals(r, flags);
+        if (rc) return peer_fail(ctx, r->ctx, rc);
+    }
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    BM_HIP(ctx, ctx_drain(ctx));  // a lazy tri_orig rebuild on a render target's stream may still read the normals
+    if (!m->corners_valid) {
+        const int32_t rc = mesh_build_corners(m);
+        if (rc) return rc;
+    }
+    const uint32_t nv = m->num_vertices;
+    GrowGuard grow{ctx};
+    BM_HIP(ctx, grow.reserve(m->slot[BM_VERTEX_DATA_NORMAL], sizeof(float) * 3 * (size_t)nv));
+    m->slot_comp[BM_VERTEX_DATA_NORMAL] = 3;
+    const uint32_t* table = m->corners.as<const uint32_t>();
+    BM_HIP(ctx, bm::launch_vertex_normals(m->slot[BM_VERTEX_DATA_POSITION].as<const float>(),
+                                          m->idx.as<const uint32_t>(), table, table + nv + 1,
+                                          m->slot[BM_VERTEX_DATA_NORMAL].as<float>(), nv,
+                                          (flags & BM_NORMALS_NORMALIZE) != 0, ctx->stream));
+    return BM_ERROR_ALL_FINE;
 }
 
 // ---- scene (Scene.cpp, SceneTree.cpp) --------------------------------------------------------
@@ -3020,6 +3160,17 @@ int32_t bm_rt_debug_tile_costs(bm_rt* rt, uint32_t n, const uint32_t* set, uint3
         BM_HIP(ctx, hipMemcpyAsync(get, rt->tile_cost.p, bytes, hipMemcpyDeviceToHost, st));
     }
     BM_HIP(ctx, hipStreamSynchronize(st));  // the host words are consumed / delivered on return
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_debug_vertex_normals(bm_context* ctx, const float* pos_dev, const uint32_t* idx_dev,
+                                const uint32_t* table_dev, float* nrm_dev, uint32_t nv, uint32_t flags) {
+    if (!ctx) return BM_ERROR_INVALID_PARAMETER;
+    if ((flags & ~BM_NORMALS_NORMALIZE) || (nv && (!pos_dev || !table_dev || !nrm_dev)))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, "debug_vertex_normals: null pointer or unknown flag bits");
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    BM_HIP(ctx, bm::launch_vertex_normals(pos_dev, idx_dev, table_dev, table_dev + nv + 1, nrm_dev, nv,
+                                          (flags & BM_NORMALS_NORMALIZE) != 0, ctx->stream));
     return BM_ERROR_ALL_FINE;
 }
 

@@ -311,6 +311,12 @@ static_assert(sizeof(XformRow) == 128, "XformRow is uploaded as a byte image: no
 hipError_t launch_instance_xform(const XformRow* rows, const uint32_t* prefix, uint32_t num_entries,
                                  uint32_t num_units, hipStream_t s);
 
+// ---- vertex normals (bm_normals.hip): a mesh's normal slot from its positions and indices ------------------
+// offsets[nv + 1] and corners[num_indices]: the vertex -> corner table, the corner ids 3f + k stably sorted by
+// their vertex (the host builds it, bm_api.cpp). Writes 3 * nv floats at nrm; nv = 0 launches nothing.
+hipError_t launch_vertex_normals(const float* pos, const uint32_t* idx, const uint32_t* offsets,
+                                 const uint32_t* corners, float* nrm, uint32_t nv, bool normalize, hipStream_t s);
+
 // ---- reference mode (bm_kd.hip): the reference's kd-tree and march ---------------------------------
 struct KdBuild {
     const MeshDesc* meshes;
