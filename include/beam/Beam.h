@@ -301,6 +301,15 @@ class IScene {
     u32 sweepSpheres(const bm_sweep* deviceSweeps, u32 n, u32 mode, void* deviceOut) {
         return (u32)bm_scene_sweep_spheres(h_, deviceSweeps, n, mode, 0, deviceOut);
     }
+    // Extension: inside or outside, and the signed distance, of each of n points in device memory
+    // (bm_scene_signed_distances; asynchronous on the context stream). mode BM_SIGNED_DISTANCE: deviceOut is
+    // bm_hit[n], closestPoints' record with the sign bit of t set inside; BM_SIGNED_OCCUPANCY: uint8_t[n].
+    // flags: 0 (one sample direction) or BM_SIGNED_VOTE3 (the majority of three). deviceVotes (optional):
+    // uint8_t[n], the votes for inside.
+    u32 signedDistances(const bm_point* devicePoints, u32 n, u32 mode, u32 flags, void* deviceOut,
+                        uint8_t* deviceVotes = nullptr) {
+        return (u32)bm_scene_signed_distances(h_, devicePoints, n, mode, flags, deviceOut, deviceVotes);
+    }
     // Extension: the triangles that intersect each of n axis-aligned boxes in device memory
     // (bm_scene_overlap_boxes; asynchronous on the context stream). mode BM_BOXES_COUNT: deviceOut is
     // uint32_t[n]; BM_BOXES_ANY: uint8_t[n]; BM_BOXES_LIST: the ids go to deviceIds at the segments of

@@ -676,6 +676,66 @@ int32_t bm_scene_sweep_spheres(bm_scene* s, const bm_sweep* sweeps_dev, uint32_t
 int32_t bm_scene_sweep_spheres_counters(bm_scene* s, const bm_sweep* sweeps_dev, uint32_t n, uint32_t mode,
                                         uint32_t flags, void* out_dev, uint64_t out[4]);
 
+/* ---- signed-distance and occupancy queries: inside or outside, for each point of a batch --------
+ * The sign the closest-point section leaves out. For point i: is it inside the scene's surface, and what
+ * is its signed distance — SDF grids for collision and learning, inside from outside after a
+ * voxelisation, the penetration depth of a sphere collider whose centre has gone through the surface, the
+ * sign at the end of a simulate / upload / normals / refit / query loop. One call and one launch instead
+ * of a ray batch, a crossing count, its parity and a second closest-point launch merged by hand.
+ * points_dev and out_dev are device pointers on the context's device, 16-byte aligned; votes_dev needs no
+ * alignment. The work is enqueued on the context stream and the call returns without waiting; bm_sync
+ * waits. On a multi-device context the query runs on the root device alone.
+ * Inside: the sign is crossing parity along fixed sample directions, not pseudonormals or winding
+ *   numbers: it asks nothing of the index topology (unshared OBJ ingest, a mesh added twice and
+ *   instanced scenes are triangle soups) and is a function of the triangle set alone. For sample
+ *   direction D_j the crossing count C_j(p) is the number of ALL triangles of the scene that the
+ *   multi-hit section's triangle function accepts for the ray (origin = p, dir = D_j, tmax = +inf):
+ *   0 < t < FLT_MAX, no filter — bm_scene_trace_rays_multi's count with k = 0 and BM_MULTI_COUNT_ALL,
+ *   exactly. The vote is v_j = C_j & 1. Without BM_SIGNED_VOTE3, inside = v_0; with it,
+ *   inside = (v_0 + v_1 + v_2 >= 2).
+ *   D0 = (a, b, c), D1 = (-b, c, a), D2 = (c, -a, b) with the float32 constants a = BM_SIGNED_DA,
+ *   b = BM_SIGNED_DB, c = BM_SIGNED_DC below (0.80901694, 0.309017, 0.2317616). They have no zero
+ *   component and no small-integer ratios, so grid-aligned points against axis-aligned or 45-degree
+ *   geometry do not send rays through edges: the triangle function accepts u = 0, v = 0 and u + v = 1,
+ *   so a ray through an edge shared by two triangles counts both, and the directions (1,0,0) and (1,1,1)
+ *   get hundreds of the points of a 1/8 grid around a cube or an octahedron wrong where these get none.
+ *   A closed mesh that is added twice flips the parity back: every point is then outside.
+ * votes_dev may be NULL; otherwise it is uint8_t[n] and votes_dev[i] is the sum of the votes taken,
+ *   0..1 or with BM_SIGNED_VOTE3 0..3. With BM_SIGNED_VOTE3 a value of 1 or 2 tells the caller that the
+ *   mesh is open or that a ray grazed it there.
+ * BM_SIGNED_DISTANCE: out_dev is bm_hit[n]. u, v, tri_id and |t| are what bm_scene_closest_points writes
+ *   for the same point record, bit for bit (the same dd function, the same (dd, id) minimum, rmax
+ *   honoured); the sign bit of t is set when the point is inside, so a point on the surface gives +0 or
+ *   -0. With no triangle within rmax the record is the miss record with t = -inf inside and +inf
+ *   outside: a narrow-band SDF keeps its sign outside the band. The record feeds
+ *   bm_scene_hit_attributes as it is (the id decides a miss there, not t).
+ * BM_SIGNED_OCCUPANCY: out_dev is uint8_t[n], 1 inside and 0 outside. No nearest traversal; rmax is not
+ *   read.
+ * Invalid points: a non-finite component of p; in distance mode also rmax NaN or <= 0. An invalid point
+ *   gives the +inf miss record, or 0, and vote 0, and is not traversed. Over an empty built scene every
+ *   point is outside.
+ * Range: the parity rays go through the ray query's box test, so the BM_ENVELOPE_EXTENTS note of
+ *   bm_camera_trace applies to them: points within that many scene extents of the scene.
+ * Points are taken in the order given, 16 consecutive points per wave, as by bm_scene_closest_points.
+ * BM_ERROR_INVALID_PARAMETER: a null handle, a null points_dev or out_dev with n > 0, a misaligned
+ * points_dev or out_dev, an unknown mode or flag bit, a scene of a reference-mode, BVH2 or BVH8 context.
+ * BM_ERROR_NOT_BUILT: the scene has no current build. n = 0 succeeds without a launch. */
+#define BM_SIGNED_DISTANCE 0u /* mode */
+#define BM_SIGNED_OCCUPANCY 1u
+#define BM_SIGNED_VOTE3 1u /* flag */
+#define BM_SIGNED_DA 0x1.9e3778p-1f
+#define BM_SIGNED_DB 0x1.3c6ef4p-2f
+#define BM_SIGNED_DC 0x1.daa5d4p-3f
+int32_t bm_scene_signed_distances(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t mode,
+                                  uint32_t flags, void* out_dev, uint8_t* votes_dev);
+/* The counting build of the same query: out[0] BVH node records fetched by the nearest phase, out[1] its
+ * triangle evaluations (both as bm_scene_closest_points_counters counts them; 0 in occupancy mode), out[2]
+ * node records fetched by the parity phase, out[3] the parity phase's triangle tests (a leaf's triangle
+ * count per leaf reached), both summed over the directions taken; invalid points count nothing. Results
+ * are written exactly as bm_scene_signed_distances writes them. Synchronous. */
+int32_t bm_scene_signed_distances_counters(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t mode,
+                                           uint32_t flags, void* out_dev, uint8_t* votes_dev, uint64_t out[4]);
+
 /* ---- box overlap queries: the triangles that intersect each box of a batch ---------------------
  * The third family beside rays and points: volumes. For axis-aligned box i: which triangles of the
  * scene touch it — voxelising a mesh into an occupancy grid, selecting a region, the broad phase of

@@ -111,6 +111,10 @@ class Sweep(C.Structure):
 
 
 SWEEP_CLOSEST, SWEEP_ANY = 0, 1  # its modes
+SIGNED_DISTANCE, SIGNED_OCCUPANCY = 0, 1  # bm_scene_signed_distances' modes
+SIGNED_VOTE3 = 1                          # its flag: the majority of three sample directions
+# the float32 constants a, b, c of its sample directions D0 = (a, b, c), D1 = (-b, c, a), D2 = (c, -a, b)
+SIGNED_DA, SIGNED_DB, SIGNED_DC = float.fromhex("0x1.9e3778p-1"), float.fromhex("0x1.3c6ef4p-2"), float.fromhex("0x1.daa5d4p-3")
 
 
 class Box(C.Structure):
@@ -220,6 +224,8 @@ SIGNATURES = {
     "bm_scene_closest_points_multi_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _U64P]),
     "bm_scene_sweep_spheres": (_I, [_P, _P, _U, _U, _U, _P]),
     "bm_scene_sweep_spheres_counters": (_I, [_P, _P, _U, _U, _U, _P, _U64P]),
+    "bm_scene_signed_distances": (_I, [_P, _P, _U, _U, _U, _P, _P]),
+    "bm_scene_signed_distances_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _U64P]),
     "bm_scene_overlap_boxes": (_I, [_P, _P, _U, _U, _U, _P, _P, _P]),
     "bm_scene_overlap_boxes_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _U64P]),
     "bm_scene_overlap_triangles": (_I, [_P, _P, _U, _U, _U, _P, _P, _P]),

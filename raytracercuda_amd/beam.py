@@ -1105,6 +1105,120 @@ class IScene:
             res["counters"] = cnt
         return res
 
+    def signedDistancesDevice(self, points, n: int, out, mode: int = _lib.SIGNED_DISTANCE, flags: int = 0,
+                              votes=0, counters=None) -> int:
+        """bm_scene_signed_distances on the device: `points` is n bm_point records of 16 bytes, `out` n bm_hit
+        records of 16 bytes (SIGNED_DISTANCE) or n bytes (SIGNED_OCCUPANCY), both 16-byte aligned, `votes` 0 or
+        n bytes of any alignment; each a raw device pointer or a torch tensor on the context's device. flags: 0
+        or SIGNED_VOTE3. Returns the error code. Asynchronous on the context stream unless `counters` (a
+        uint64[4] numpy array to fill) is given."""
+        pp = C.c_void_p((points.data_ptr() if hasattr(points, "data_ptr") else points) or None)
+        op = C.c_void_p((out.data_ptr() if hasattr(out, "data_ptr") else out) or None)
+        vp = C.c_void_p((votes.data_ptr() if hasattr(votes, "data_ptr") else votes) or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_signed_distances(self.h, pp, n, mode, flags, op, vp)
+        return self.ctx.lib.bm_scene_signed_distances_counters(self.h, pp, n, mode, flags, op, vp,
+                                                               counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def _signed(self, who: str, points, rmax, mode: int, vote3: bool, votes: bool, counters: bool):
+        """The shared path of signedDistance and occupancy: closestPoints' packing and stream rules."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        on_device = isinstance(points, torch.Tensor)
+        if on_device:
+            if points.dim() == 2 and points.shape[1] == 4 and rmax is None:
+                pts = points
+            elif points.dim() == 2 and points.shape[1] == 3:
+                pts = torch.empty((points.shape[0], 4), dtype=torch.float32, device=points.device)
+                pts[:, 0:3] = points
+                pts[:, 3] = float("inf") if rmax is None else rmax
+            else:
+                raise BeamError(ERROR_INVALID_PARAMETER, who + ": points are (n, 3), or packed (n, 4), float32")
+            if pts.device != dev or pts.dtype != torch.float32 or not pts.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"{who}: points must be contiguous float32 on {dev} (the context's device)")
+        else:
+            q = _f32(points).reshape(-1, 3)
+            packed = np.zeros((q.shape[0], 4), np.float32)
+            packed[:, 0:3] = q
+            packed[:, 3] = np.inf if rmax is None else rmax
+            pts = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = pts.shape[0]
+        dist = mode == _lib.SIGNED_DISTANCE
+        out = (torch.empty((n, 4), dtype=torch.float32, device=dev) if dist
+               else torch.empty((n,), dtype=torch.uint8, device=dev))
+        vt = torch.empty((n,), dtype=torch.uint8, device=dev) if votes else None
+        cnt = np.zeros(4, np.uint64) if counters else None
+        self.ctx._check(self.signedDistancesDevice(pts.data_ptr() if n else 0, n, out.data_ptr() if n else 0, mode,
+                                                   _lib.SIGNED_VOTE3 if vote3 else 0,
+                                                   vt.data_ptr() if votes and n else 0, cnt))
+        self._points_keep = pts  # until the next query: the kernel may not have read them yet
+        if dist:
+            res = {"hits": out, "t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "tri_id": out.view(torch.int32)[:, 3]}
+        else:
+            res = {"inside": out.view(torch.bool)}
+        if votes:
+            res["votes"] = vt
+        if not on_device:
+            self.ctx.sync()
+            if dist:
+                h = out.cpu().numpy()
+                res = {"t": h[:, 0].copy(), "u": h[:, 1].copy(), "v": h[:, 2].copy(),
+                       "tri_id": h.view(np.uint32)[:, 3].copy()}
+            else:
+                res = {"inside": out.cpu().numpy().astype(bool)}
+            if votes:
+                res["votes"] = vt.cpu().numpy()
+        if counters:
+            res["counters"] = cnt
+        return res
+
+    def signedDistance(self, points, rmax=None, vote3: bool = False, votes: bool = False, counters: bool = False):
+        """The signed distance of n points to the scene (bm_scene_signed_distances, SIGNED_DISTANCE): what
+        closestPoints returns for the same points and rmax, with the sign bit of t set where the point is
+        inside — crossing parity along one fixed direction, or with vote3 the majority of three. A point with
+        no triangle within rmax gets t = -inf inside and +inf outside (tri_id = NO_TRIANGLE either way).
+        Inputs, outputs and stream rules as closestPoints: numpy in, numpy out after a wait; torch tensors stay
+        on the device and nothing waits ("hits" goes straight into hitAttributes).
+        votes=True adds "votes": uint8 (n,), the votes for inside (0..1, or 0..3 with vote3; 1 or 2 of 3 marks
+        an open mesh or a grazing ray). counters=True adds "counters": [nearest-phase node records and triangle
+        evaluations, parity-phase node records and triangle tests] (waits)."""
+        return self._signed("signedDistance", points, rmax, _lib.SIGNED_DISTANCE, vote3, votes, counters)
+
+    def occupancy(self, points, vote3: bool = False, votes: bool = False):
+        """Inside or outside for n points (bm_scene_signed_distances, SIGNED_OCCUPANCY): {"inside": bool (n,)}
+        and with votes=True "votes" as signedDistance gives them. No distance is computed. numpy (n,3) points
+        in, numpy out after a wait; torch (n,3) or packed (n,4) points stay on the device and nothing waits."""
+        return self._signed("occupancy", points, None, _lib.SIGNED_OCCUPANCY, vote3, votes, False)
+
+    def sdfGrid(self, lo, hi, dims, rmax=None, vote3: bool = True):
+        """The signed distance at the cell centres of a regular grid: a float32 tensor of shape dims =
+        (nx, ny, nz) on the context's device (a view of the records' t column), negative inside (signedDistance over the centres; beyond rmax
+        the value is -inf or +inf). The centres are voxelize's, made on the device by the same float32
+        statements, cell (i, j, k) being point (i * ny + j) * nz + k of the batch; the stream rules are
+        voxelize's too."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        dims = tuple(int(d) for d in dims)
+        if len(dims) != 3 or min(dims) < 1:
+            raise BeamError(ERROR_INVALID_PARAMETER, "sdfGrid: dims is three positive integers")
+        lo32, hi32 = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        cell = (hi32 - lo32) / np.asarray(dims, np.float32)
+        n = dims[0] * dims[1] * dims[2]
+        pts = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        grid = pts.view(dims[0], dims[1], dims[2], 4)
+        for a in range(3):  # one multiply and one add per component, as voxelize
+            idx = torch.arange(dims[a], dtype=torch.float32, device=dev)
+            axis = float(lo32[a]) + (idx + 0.5) * float(cell[a])
+            shape = [1, 1, 1]
+            shape[a] = dims[a]
+            grid[..., a] = axis.view(shape)
+        grid[..., 3] = float("inf") if rmax is None else float(rmax)
+        torch.cuda.current_stream(dev).synchronize()  # the points, before the context stream reads them
+        # the t column of the records as a strided view: no copy, so nothing runs on another stream
+        return self.signedDistance(pts, vote3=vote3)["hits"].view(dims[0], dims[1], dims[2], 4)[..., 0]
+
     def hitAttributesDevice(self, hits_ptr: int, n: int, requests) -> int:
         """bm_scene_hit_attributes on device pointers: n bm_hit records of 16 bytes in, and per request
         (slot, components, flags, out_ptr[, pad]) n rows of `components` 4-byte words out, every pointer

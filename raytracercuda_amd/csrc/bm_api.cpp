@@ -2088,6 +2088,8 @@ static int32_t trace_impl(bm_camera* c, const float* eye3, const float* orient3x
 // One path for both: the checks in the order beam_c.h lists them, the quad kernels' launch parameters on the
 // context stream with the overflow area reserved, the launch, and for the counting forms the counters read
 // back (3 words for rays, 4 for points; synchronous). points: a closest-point query (mode is not read).
+// Signed queries (bm_signed.hip) take the same path: their flag is BM_SIGNED_VOTE3, and votes (may be null,
+// any alignment) travels in TraceParams::q_counts.
 // The filter bits of a ray query (beam_c.h): known bits only, one cull flag, one meaning for pad.
 static bool filter_flags_valid(uint32_t f) {
     constexpr uint32_t pad_bits = BM_RAYS_PAD_SKIP_TRI | BM_RAYS_PAD_TMIN | BM_RAYS_PAD_MASK;
@@ -2144,20 +2146,26 @@ static int32_t filter_setup(bm_scene* s, uint32_t flags, hipStream_t st, bm::Tra
     return BM_ERROR_ALL_FINE;
 }
 
-enum QueryKernel { QUERY_RAYS, QUERY_POINTS, QUERY_SWEEPS };  // which kernel query_impl's path ends in
+enum QueryKernel { QUERY_RAYS, QUERY_POINTS, QUERY_SWEEPS, QUERY_SIGNED };  // which kernel query_impl's path ends in
 
 static int32_t query_impl(bm_scene* s, QueryKernel kernel, const void* in, uint32_t n, uint32_t mode, uint32_t flags,
-                          void* out, uint64_t* counters) {
+                          void* out, uint64_t* counters, uint8_t* votes = nullptr) {
     if (!s) return BM_ERROR_INVALID_PARAMETER;
     bm_context* ctx = s->ctx;
     const bool rays = kernel == QUERY_RAYS;
-    const std::string who = kernel == QUERY_POINTS ? "closest_points: " : rays ? "trace_rays: " : "sweep_spheres: ";
+    const std::string who = kernel == QUERY_POINTS   ? "closest_points: "
+                            : kernel == QUERY_SIGNED ? "signed_distances: "
+                            : rays                   ? "trace_rays: "
+                                                     : "sweep_spheres: ";
     if (n && (!in || !out)) return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "null input or result pointer");
     if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "input and result pointers must be 16-byte aligned");
     static_assert(BM_SWEEP_ANY == BM_RAYS_ANY_HIT, "one mode check serves rays and sweeps");
+    static_assert(BM_SIGNED_OCCUPANCY == BM_RAYS_ANY_HIT, "and the signed queries' two modes");
     if ((kernel != QUERY_POINTS && mode > BM_RAYS_ANY_HIT) ||
-        (rays ? !filter_flags_valid(flags) : flags != 0))  // points and sweeps: no flag bits
+        (rays                     ? !filter_flags_valid(flags)
+         : kernel == QUERY_SIGNED ? (flags & ~BM_SIGNED_VOTE3) != 0
+                                  : flags != 0))  // points and sweeps: no flag bits
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "unknown mode or flag bits");
     if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
@@ -2180,6 +2188,7 @@ static int32_t query_impl(bm_scene* s, QueryKernel kernel, const void* in, uint3
     p.q_rays = reinterpret_cast<const float4*>(in);
     p.q_out = out;
     p.q_n = n;
+    p.q_counts = reinterpret_cast<uint32_t*>(votes);  // signed queries: a byte per point
     if (rays)
         if (const int32_t e = filter_setup(s, flags, st, p)) return e;
     if (const int32_t e = reserve_overflow(ctx, nullptr, st, p)) return e;
@@ -2188,9 +2197,11 @@ static int32_t query_impl(bm_scene* s, QueryKernel kernel, const void* in, uint3
         BM_HIP(ctx, hipMemsetAsync(ctx->rays_counters, 0, 4 * sizeof(unsigned long long), st));
         p.counters = ctx->rays_counters;
     }
-    BM_HIP(ctx, kernel == QUERY_POINTS ? bm::launch_closest_points(p, counters != nullptr, st)
-                : rays                 ? bm::launch_query_rays(p, mode, counters != nullptr, st)
-                                       : bm::launch_sweep_spheres(p, mode, counters != nullptr, st));
+    BM_HIP(ctx, kernel == QUERY_POINTS   ? bm::launch_closest_points(p, counters != nullptr, st)
+                : kernel == QUERY_SIGNED ? bm::launch_signed_points(p, mode, (flags & BM_SIGNED_VOTE3) != 0,
+                                                                    counters != nullptr, st)
+                : rays                   ? bm::launch_query_rays(p, mode, counters != nullptr, st)
+                                         : bm::launch_sweep_spheres(p, mode, counters != nullptr, st));
     if (counters) {
         unsigned long long h[4];
         BM_HIP(ctx, hipMemcpyAsync(h, ctx->rays_counters, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -2230,6 +2241,17 @@ int32_t bm_scene_sweep_spheres_counters(bm_scene* s, const bm_sweep* sweeps_dev,
                                         uint32_t flags, void* out_dev, uint64_t out[4]) {
     if (!out) return BM_ERROR_INVALID_PARAMETER;
     return query_impl(s, QUERY_SWEEPS, sweeps_dev, n, mode, flags, out_dev, out);
+}
+
+int32_t bm_scene_signed_distances(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                                  void* out_dev, uint8_t* votes_dev) {
+    return query_impl(s, QUERY_SIGNED, points_dev, n, mode, flags, out_dev, nullptr, votes_dev);
+}
+
+int32_t bm_scene_signed_distances_counters(bm_scene* s, const bm_point* points_dev, uint32_t n, uint32_t mode,
+                                           uint32_t flags, void* out_dev, uint8_t* votes_dev, uint64_t out[4]) {
+    if (!out) return BM_ERROR_INVALID_PARAMETER;
+    return query_impl(s, QUERY_SIGNED, points_dev, n, mode, flags, out_dev, out, votes_dev);
 }
 
 // ---- multi-result queries: rays (bm_multihit.hip) and points (bm_points_multi.hip) ---------------

@@ -261,6 +261,13 @@ hipError_t launch_overlap_triangles(const TraceParams& p, uint32_t mode, bool co
 // up as for launch_closest_points. count: into p.counters[0..3] (node records, triangle evaluations, sweeps
 // with a result, the deepest stack held).
 hipError_t launch_sweep_spheres(const TraceParams& p, uint32_t mode, bool count, hipStream_t s);
+// Signed-distance / occupancy query (bm_signed.hip): for each of p.q_n points (one float4 (p, rmax) each in
+// p.q_rays) the crossing parity along one or, with vote3, three fixed directions; BM_SIGNED_DISTANCE: one
+// bm_hit each into p.q_out, launch_closest_points' record with the sign on t; BM_SIGNED_OCCUPANCY: one byte.
+// p.q_counts, where not null, is a uint8_t[q_n] for the votes (the field serves under its multi-hit name so
+// that TraceParams stays as it is). Set up as for launch_closest_points. count: into p.counters[0..3] (the
+// nearest phase's node records and triangle evaluations, the parity phase's node records and triangle tests).
+hipError_t launch_signed_points(const TraceParams& p, uint32_t mode, bool vote3, bool count, hipStream_t s);
 // ---- hit attributes (bm_attrs.hip): vertex slots interpolated at the hits of a ray query ------------
 // One entry per scene mesh, in scene order: every slot's device buffer (null: the mesh has none), so the
 // table depends on the meshes alone and not on what a call requests.

@@ -4,7 +4,8 @@
 // or the owning mesh and face.
 //   k_closest_points  persistent grid; a wave takes batches of 16 consecutive points (256 contiguous
 //                     bytes), lane 4q+c works for point 16b+q — the shape of k_query_rays
-// The traversal (quad_nearest) is distance ordered over the BVH4: lane c takes child c's squared box
+// The traversal (quad_nearest, in bm_query_dev.h since bm_signed.hip shares it) is distance ordered over
+// the BVH4: lane c takes child c's squared box
 // distance, the kept children are ranked by order_key and pushed farthest first with that distance as
 // their stack key, and a subtree is dropped when its box lies beyond a widened image of the best squared
 // distance found so far. The widening makes the pruning conservative against the rounding of the
@@ -14,75 +15,6 @@
 
 namespace bm {
 namespace {
-
-// Nearest triangle of one point over the quad: the lexicographic minimum of (dd, id) over the triangles
-// with dd <= best on entry (rmax^2). One iteration is quad_closest's: the pending leaf, the pop that
-// follows it, the node visit. The bound moves only when best improves: a handful of times per query.
-// maxsp (COUNT): the most stack entries held at once.
-template <bool COUNT, uint32_t PRIO, typename QS>
-__device__ __forceinline__ void quad_nearest(const TraceParams& p, const QS& st, int c, const vec3f pt, float m,
-                                             float& best, uint32_t& ibest, float& bu, float& bv,
-                                             unsigned long long& cn, unsigned long long& ct, int& maxsp) {
-    int sp = 0;
-    uint32_t next = p.num_tris ? 0u : EMPTY_REF;
-    uint32_t iter = 0;
-    float bound = widen(best, m);
-    for (;;) {
-        prio_boost<PRIO>(p, iter);
-        if (next != EMPTY_REF && (next & LEAF_BIT)) {
-            const uint32_t first = next & FIRST_MASK, cnt = ((next >> 27) & 15u) + 1u;
-            bool better = false;
-            for (uint32_t k0 = 0; k0 < cnt; k0 += 4) {
-                const uint32_t k = first + k0 + c;
-                float dd = __builtin_inff(), u = 0.f, v = 0.f;
-                uint32_t id = NO_TRI;
-                if (k0 + c < cnt) {
-                    const float4 a = p.tris[3 * k + 0], b = p.tris[3 * k + 1], cc = p.tris[3 * k + 2];
-                    float d, uu, vv;
-                    tri_nearest(a, b, cc, pt, d, uu, vv);
-                    if (d == d) dd = d, u = uu, v = vv, id = f2u(a.w);  // NaN: never a candidate
-                }
-                quad_min_hit(dd, id, u, v);
-                if (dd < best || (dd == best && id < ibest)) {
-                    best = dd;
-                    ibest = id;
-                    bu = u;
-                    bv = v;
-                    better = true;
-                }
-            }
-            if (better) bound = widen(best, m);
-            if (COUNT && c == 0) ct += cnt;
-            next = EMPTY_REF;
-        }
-        if (next == EMPTY_REF) {
-            bool found = false;
-            while (sp > 0) {
-                --sp;
-                uint32_t ref;
-                float key;
-                st.get(sp, ref, key);
-                if (!(key > bound)) {
-                    next = ref;
-                    found = true;
-                    break;
-                }
-            }
-            if (!found) break;
-            if (next & LEAF_BIT) continue;  // a popped leaf: evaluated at the top of the next iteration
-        }
-        if (COUNT && c == 0) ++cn;
-        next = nearest_visit(p, next, c, pt, bound, st, sp);
-        if (COUNT) maxsp = max(maxsp, sp);
-#pragma unroll
-        for (int extra = 1; extra < QUAD_VISITS; ++extra) {
-            if (next == EMPTY_REF || (next & LEAF_BIT)) break;
-            if (COUNT && c == 0) ++cn;
-            next = nearest_visit(p, next, c, pt, bound, st, sp);
-            if (COUNT) maxsp = max(maxsp, sp);
-        }
-    }
-}
 
 // A point record is one float4 (p, rmax); the four lanes of a quad load the same 16 bytes. An invalid
 // point (a non-finite component of p; rmax NaN or <= 0) is finished here with the miss record, so no NaN
