@@ -325,6 +325,17 @@ class IScene {
                          const uint32_t* deviceOffsets = nullptr, uint32_t* deviceIds = nullptr, u32 flags = 0) {
         return (u32)bm_scene_overlap_triangles(h_, deviceTris, n, mode, flags, deviceOut, deviceOffsets, deviceIds);
     }
+    // Extension: the triangles each of n planes in device memory crosses, and their cut segments
+    // (bm_scene_section_planes; asynchronous on the context stream). mode BM_PLANES_COUNT: deviceOut is
+    // uint32_t[n]; BM_PLANES_ANY: uint8_t[n]; BM_PLANES_LIST: slot j of plane i goes to deviceIds and/or
+    // deviceSegments (at least one) at deviceOffsets[i] + j (n + 1 ascending values), the counts to deviceOut
+    // unless it is null. On a closed mesh the segments chain into closed loops by equality of their endpoints.
+    u32 sectionPlanes(const bm_plane* devicePlanes, u32 n, u32 mode, void* deviceOut,
+                      const uint32_t* deviceOffsets = nullptr, uint32_t* deviceIds = nullptr,
+                      bm_segment* deviceSegments = nullptr) {
+        return (u32)bm_scene_section_planes(h_, devicePlanes, n, mode, 0, deviceOut, deviceOffsets, deviceIds,
+                                            deviceSegments);
+    }
     // Extension: instance transforms (include/beam_c.h, "instance transforms"). xform: 12 floats, row-major
     // 3x4 (xformFromColumnMajor4x4 converts a glm::mat4's 16 floats). addInstance appends the mesh at that
     // placement and reports the entry's index; setInstanceTransform takes effect at the next updateGPUScene

@@ -897,6 +897,96 @@ int32_t bm_scene_overlap_triangles_counters(bm_scene* s, const bm_tri* tris_dev,
                                             uint32_t flags, void* out_dev, const uint32_t* offsets_dev,
                                             uint32_t* ids_dev, uint64_t out[4]);
 
+/* ---- plane section queries: the triangles each plane of a batch crosses, and their cut segments -----
+ * The fourth family: planes. For plane i: where does it cut the scene — the layers of a slicer, cross-sections
+ * and contour lines, the cap polygon of a clipping plane, cutting planes of tool paths, the outline a boolean
+ * or remeshing step starts from. An unordered traversal of the same BVH4 that follows every child box with a
+ * corner on each side of the plane.
+ * planes_dev is a device pointer on the context's device, 16-byte aligned, and so is segs_dev; out_dev,
+ * offsets_dev and ids_dev are 4-byte aligned (the byte plane of BM_PLANES_ANY: any address). The work is
+ * enqueued on the context stream and the call returns without waiting; bm_sync waits. On a multi-device
+ * context the query runs on the root device alone.
+ * The plane passes through `point` and is perpendicular to `normal`, which need not have unit length.
+ * The query is stated on the meshes' own vertices, not on the build's (v0, e1, e2) records: triangle g's
+ *   positions x0, x1, x2 are read through its mesh's index triple, in index order, from the mesh's position
+ *   slot (an instanced entry: from the scene's world-space copy of the last build or refit). Float32
+ *   throughout, one rounding per operation in the order written, never contracted; a comparison with NaN is
+ *   false.
+ *     For a position x:  d = x - point (per component),  s(x) = (n.x*d.x + n.y*d.y) + n.z*d.z.
+ *     x is BELOW when s(x) < 0, otherwise ABOVE: s = +0 or -0 is above, so a vertex on the plane belongs to
+ *     the positive side.
+ *     Triangle g is CROSSED when at least one of its vertices is below and at least one is above.
+ *   C_i is the set of ALL crossed triangles of the scene. Consequences of the rule:
+ *     a triangle lying in the plane is not crossed (all three vertices are above);
+ *     a triangle that touches the plane from above (a vertex or an edge on it, the rest above) is not crossed;
+ *     a triangle that touches the plane from below is crossed, with a segment of length zero (a vertex on
+ *     the plane) or the touching edge itself;
+ *     both triangles on a mesh edge see the same sides of its two ends, which is what makes every loop close.
+ * The segment of a crossed triangle: going x0 -> x1 -> x2 -> x0, exactly one edge runs from above to below
+ *   (the down edge) and exactly one from below to above (the up edge). a is the cut of the down edge and b
+ *   the cut of the up edge; seen from the triangle's front (the side its counter-clockwise winding faces),
+ *   the above side lies to the left of a -> b.
+ *   The cut of an edge with below end N and above end P, whichever way the edge runs:
+ *     t = s(N) / (s(N) - s(P))         and per component  X = t*P + (N - t*N)
+ *   s(N) < 0 <= s(P), so the denominator is never zero and t lies in (0, 1]; t = 1 exactly when P is on the
+ *   plane, and X is then P (bit for bit, up to the sign of a zero component).
+ *   X depends only on the two positions' bits and the plane: the two triangles on an edge compute identical
+ *   bits whatever their vertex indices, unwelded (duplicated) vertices included. On a consistently oriented
+ *   closed manifold each crossed edge is one triangle's up edge and the other's down edge, so the multiset of
+ *   the b equals the multiset of the a bit for bit, and the segments chain into closed loops by plain
+ *   equality of endpoints, with no welding tolerance.
+ * mode BM_PLANES_COUNT: out_dev is uint32_t[n], out_dev[i] = |C_i|. offsets_dev, ids_dev, segs_dev ignored.
+ * mode BM_PLANES_ANY: out_dev is uint8_t[n], out_dev[i] = 1 when C_i is not empty, else 0. The traversal of
+ *   a plane ends at the first crossed triangle.
+ * mode BM_PLANES_LIST: a CSR fill by BM_BOXES_LIST's rules. offsets_dev is uint32_t[n + 1], ascending. At
+ *   least one of ids_dev and segs_dev is not null; slot j of plane i goes to ids_dev[offsets_dev[i] + j]
+ *   (the triangle's global id) and/or segs_dev[offsets_dev[i] + j] (a, the id, b, and the plane's index i, so
+ *   the flat array is self-contained), at most offsets_dev[i+1] - offsets_dev[i] slots; nothing is ever
+ *   written outside a plane's own segment, and the unused tail of a segment is left untouched. out_dev may
+ *   be NULL; otherwise it is uint32_t[n] and out_dev[i] = |C_i|. The order inside a segment is the
+ *   traversal's: the same for every call on the same build, on every GPU and grid size (nothing is decided
+ *   by an atomic), and otherwise unspecified. A segment that is too short holds the first entries of it.
+ * Invalid planes (a non-finite component of point or normal; a normal of all zeros) are not looked up:
+ *   count 0, byte 0, nothing listed. The pad words are ignored. Over an empty built scene every count and
+ *   byte is 0.
+ * The bit-for-bit guarantee holds while no operation in s (the three differences, the three products, the two
+ *   additions) overflows over the scene's bounding box; beyond that the result is unspecified (and
+ *   memory-safe).
+ * Precondition: positions uploaded to a mesh since the last build or refit need a refit (or build) first —
+ *   the tree bounds the positions it was made from, the query reads the current ones.
+ *   BM_ERROR_NOT_BUILT when the scene's meshes or their index counts are no longer the build's, as for
+ *   bm_scene_hit_attributes.
+ * flags: none defined yet, pass 0. Planes are taken in the order given, 16 consecutive planes per wave.
+ * BM_ERROR_INVALID_PARAMETER: a null handle; with n > 0 a null planes_dev, a null out_dev unless the mode is
+ * BM_PLANES_LIST, with BM_PLANES_LIST a null offsets_dev or both of ids_dev and segs_dev null; a misaligned
+ * pointer; an unknown mode or flag bit; a scene of a reference-mode, BVH2 or BVH8 context.
+ * BM_ERROR_NOT_BUILT: the scene has no current build. n = 0 succeeds without a launch. */
+typedef struct bm_plane {
+    float point[3];
+    uint32_t pad0;
+    float normal[3];
+    uint32_t pad1;
+} bm_plane; /* 32 B */
+typedef struct bm_segment {
+    float a[3];
+    uint32_t tri_id;
+    float b[3];
+    uint32_t plane;
+} bm_segment; /* 32 B */
+#define BM_PLANES_COUNT 0u
+#define BM_PLANES_ANY 1u
+#define BM_PLANES_LIST 2u
+int32_t bm_scene_section_planes(bm_scene* s, const bm_plane* planes_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                                void* out_dev, const uint32_t* offsets_dev, uint32_t* ids_dev, bm_segment* segs_dev);
+/* The counting build of the same query: out[0] BVH node records fetched, out[1] triangle tests (a leaf's
+ * triangle count per leaf reached), out[2] the sum of |C_i| (BM_PLANES_ANY: the number of planes with a
+ * crossing), out[3] the largest number of stack entries any plane held at once (above 24 the traversal used
+ * the global overflow area); invalid planes count nothing. Results are written exactly as
+ * bm_scene_section_planes writes them. Synchronous. */
+int32_t bm_scene_section_planes_counters(bm_scene* s, const bm_plane* planes_dev, uint32_t n, uint32_t mode,
+                                         uint32_t flags, void* out_dev, const uint32_t* offsets_dev,
+                                         uint32_t* ids_dev, bm_segment* segs_dev, uint64_t out[4]);
+
 /* ---- hit attributes: the meshes' vertex slots interpolated at ray-query hits ------------------
  * The reference's bmFaceInterpolate<T>(face, u, v, meshData, dataIdx) (CudaComon.cuh:253-266) over n
  * bm_hit records in device memory (as bm_scene_trace_rays writes them, or made by the caller): what a

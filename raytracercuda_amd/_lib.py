@@ -135,6 +135,19 @@ TRIS_COUNT, TRIS_ANY, TRIS_LIST = 0, 1, 2  # its modes
 TRIS_PAD_SKIP_TRI = 1  # its flag: pad0 is a triangle id that is never reported
 
 
+class Plane(C.Structure):
+    """bm_plane: one plane of bm_scene_section_planes (32 bytes: through point, perpendicular to normal)."""
+    _fields_ = [("point", C.c_float * 3), ("pad0", C.c_uint32), ("normal", C.c_float * 3), ("pad1", C.c_uint32)]
+
+
+class Segment(C.Structure):
+    """bm_segment: one cut segment of bm_scene_section_planes (32 bytes)."""
+    _fields_ = [("a", C.c_float * 3), ("tri_id", C.c_uint32), ("b", C.c_float * 3), ("plane", C.c_uint32)]
+
+
+PLANES_COUNT, PLANES_ANY, PLANES_LIST = 0, 1, 2  # its modes
+
+
 class AttrReq(C.Structure):
     """bm_attr_req: one request of bm_scene_hit_attributes (24 bytes)."""
     _fields_ = [("slot", C.c_uint32), ("components", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32),
@@ -230,6 +243,8 @@ SIGNATURES = {
     "bm_scene_overlap_boxes_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _U64P]),
     "bm_scene_overlap_triangles": (_I, [_P, _P, _U, _U, _U, _P, _P, _P]),
     "bm_scene_overlap_triangles_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _U64P]),
+    "bm_scene_section_planes": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _P]),
+    "bm_scene_section_planes_counters": (_I, [_P, _P, _U, _U, _U, _P, _P, _P, _P, _U64P]),
     "bm_scene_hit_attributes": (_I, [_P, _P, _U, C.POINTER(AttrReq), _U]),
     "bm_camera_create": (_I, [_P, C.POINTER(_P)]),
     "bm_camera_set_initial_rays": (_I, [_P, _U, _U, _F, _F, _F, _F, _F]),

@@ -961,6 +961,127 @@ class IScene:
         touch = (face[a, 0] == face[b, 0]) & (vidx[a][:, :, None] == vidx[b][:, None, :]).any(axis=(1, 2))
         return pairs[~touch]
 
+    def sectionPlanesDevice(self, planes_ptr: int, n: int, mode: int, out_ptr: int, offsets_ptr: int = 0,
+                            ids_ptr: int = 0, segs_ptr: int = 0, flags: int = 0, counters=None) -> int:
+        """bm_scene_section_planes on device pointers (n bm_plane records of 32 bytes in, 16-byte aligned; out_ptr:
+        n uint32 for PLANES_COUNT and PLANES_LIST (there it may be 0), n bytes for PLANES_ANY; PLANES_LIST:
+        offsets_ptr n + 1 uint32, and at least one of ids_ptr (uint32 per slot) and segs_ptr (a 32-byte bm_segment
+        per slot, 16-byte aligned)); returns the error code. Asynchronous on the context stream unless `counters`
+        (a uint64[4] numpy array to fill) is given. flags: none defined yet."""
+        pp, op = C.c_void_p(planes_ptr or None), C.c_void_p(out_ptr or None)
+        fp, ip, sp = C.c_void_p(offsets_ptr or None), C.c_void_p(ids_ptr or None), C.c_void_p(segs_ptr or None)
+        if counters is None:
+            return self.ctx.lib.bm_scene_section_planes(self.h, pp, n, mode, flags, op, fp, ip, sp)
+        return self.ctx.lib.bm_scene_section_planes_counters(self.h, pp, n, mode, flags, op, fp, ip, sp,
+                                                             counters.ctypes.data_as(C.POINTER(C.c_uint64)))
+
+    def sectionPlanes(self, points, normals=None, mode: str = "count", counters: bool = False):
+        """The triangles each of n planes crosses, and where it cuts them (bm_scene_section_planes). Plane i passes
+        through points[i] and is perpendicular to normals[i] (any length). A triangle is crossed when, on its
+        mesh's own vertices, s(x) = (n.x*d.x + n.y*d.y) + n.z*d.z with d = x - point is negative for at least one
+        vertex and not negative for at least one: a vertex on the plane counts as above. points (n,3) and
+        normals (n,3) (or one (3,) normal for all), or one packed (n,8) float32 array (point, pad, normal, pad).
+
+        mode "count": {"count": (n,)} the number of crossed triangles per plane. mode "any": {"any": (n,) bool}.
+        mode "list": the count pass, torch.cumsum of the counts into offsets on the device, one read of the total,
+        then the list pass: {"count": (n,), "offsets": (n + 1,), "ids": (total,)} with plane i's triangle ids in
+        ids[offsets[i]:offsets[i + 1]], in traversal order (the same on every call).
+        mode "segments": the same two passes, the list pass writing the cut segments as well; returns the tuple
+        (offsets (n + 1,), ids (total,), a (total, 3), b (total, 3)): slot j's triangle ids[j] is cut from a[j]
+        (on its edge running from above to below) to b[j] (on its edge running from below to above). The two
+        triangles on a mesh edge compute the same bits for its cut, so on a closed mesh chainSegments(a, b) of a
+        plane's slots gives closed loops.
+
+        numpy in: uploads, queries and waits; returns numpy arrays (uint32, float32; "any" bool).
+        torch tensors on the context's device: everything stays on the device (int32, float32; "any" bool);
+        "list" and "segments" wait once, for the total. Make the context on torch's stream, as for traceRays.
+        counters=True adds "counters": [node records, triangle tests, the sum of the counts (any: planes with a
+        crossing), deepest stack] of the last pass (waits); with "segments" it is a fifth tuple element."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        modes = {"count": _lib.PLANES_COUNT, "any": _lib.PLANES_ANY, "list": _lib.PLANES_LIST,
+                 "segments": _lib.PLANES_LIST}
+        if mode not in modes:
+            raise BeamError(ERROR_INVALID_PARAMETER, 'sectionPlanes: mode is "count", "any", "list" or "segments"')
+        on_device = isinstance(points, torch.Tensor)
+        if on_device:
+            if points.dim() == 2 and points.shape[1] == 8 and normals is None:
+                planes = points
+            elif points.dim() == 2 and points.shape[1] == 3 and normals is not None:
+                planes = torch.zeros((points.shape[0], 8), dtype=torch.float32, device=points.device)
+                planes[:, 0:3] = points
+                planes[:, 4:7] = normals if isinstance(normals, torch.Tensor) else torch.from_numpy(
+                    np.ascontiguousarray(np.broadcast_to(_f32(normals).reshape(-1, 3), (points.shape[0], 3)))).to(dev)
+            else:
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                "sectionPlanes: points (n, 3) with normals, or packed (n, 8), float32")
+            if planes.device != dev or planes.dtype != torch.float32 or not planes.is_contiguous():
+                raise BeamError(ERROR_INVALID_PARAMETER,
+                                f"sectionPlanes: planes must be contiguous float32 on {dev} (the context's device)")
+        else:
+            a = _f32(points)
+            if normals is None:
+                packed = np.ascontiguousarray(a.reshape(-1, 8))
+            else:
+                pts = a.reshape(-1, 3)
+                packed = np.zeros((pts.shape[0], 8), np.float32)
+                packed[:, 0:3] = pts
+                packed[:, 4:7] = _f32(normals).reshape(-1, 3)  # one normal broadcasts over the rows
+            planes = torch.from_numpy(packed).to(dev)
+            torch.cuda.current_stream(dev).synchronize()  # the upload, before the context stream reads it
+        n = planes.shape[0]
+        pptr = planes.data_ptr() if n else 0
+        cnt = np.zeros(4, np.uint64) if counters else None
+        if mode == "any":
+            out = torch.empty((n,), dtype=torch.uint8, device=dev)
+            self.ctx._check(self.sectionPlanesDevice(pptr, n, _lib.PLANES_ANY, out.data_ptr() if n else 0, counters=cnt))
+            res = {"any": out.view(torch.bool)}
+        else:
+            count = torch.empty((n,), dtype=torch.int32, device=dev)
+            if mode == "count":
+                self.ctx._check(self.sectionPlanesDevice(pptr, n, _lib.PLANES_COUNT, count.data_ptr() if n else 0,
+                                                         counters=cnt))
+                res = {"count": count}
+            else:
+                self.ctx._check(self.sectionPlanesDevice(pptr, n, _lib.PLANES_COUNT, count.data_ptr() if n else 0))
+                if not on_device:
+                    self.ctx.sync()  # the counts, before torch's stream reads them
+                offsets = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
+                torch.cumsum(count, 0, dtype=torch.int32, out=offsets[1:])
+                total = int(offsets[-1].item())  # the one read; it also puts the offsets before the list pass
+                ids = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)  # never a null pointer
+                segs = torch.empty((max(total, 1), 8), dtype=torch.float32, device=dev) if mode == "segments" else None
+                self.ctx._check(self.sectionPlanesDevice(pptr, n, _lib.PLANES_LIST, 0, offsets.data_ptr(), ids.data_ptr(),
+                                                         segs.data_ptr() if segs is not None else 0, counters=cnt))
+                res = {"count": count, "offsets": offsets, "ids": ids[:total]}
+                if segs is not None:
+                    res["a"], res["b"] = segs[:total, 0:3], segs[:total, 4:7]
+        self._planes_keep = planes  # until the next query: the kernel may not have read them yet
+        if not on_device:
+            self.ctx.sync()
+            res = {k: (v.cpu().numpy() if k in ("any", "a", "b") else v.cpu().numpy().view(np.uint32))
+                   for k, v in res.items()}
+            if mode == "segments":
+                res["a"], res["b"] = np.ascontiguousarray(res["a"]), np.ascontiguousarray(res["b"])
+        if mode == "segments":
+            out = (res["offsets"], res["ids"], res["a"], res["b"])
+            return out + (cnt,) if counters else out
+        if counters:
+            res["counters"] = cnt
+        return res
+
+    def sliceStack(self, origin, normal, heights, mode: str = "segments", counters: bool = False):
+        """A stack of parallel sections, the layers of a slicer: sectionPlanes over the planes with the one
+        `normal` (3,), plane i through the point, in float32 (numpy statements; every operation rounds once):
+            o32, n32, h32 = np.float32(origin), np.float32(normal), np.float32(heights)
+            point[i] = o32 + h32[i] * n32                                        # per component
+        heights: n numbers (a unit normal makes them distances along it). Returns what sectionPlanes returns for
+        `mode` with numpy input: for "segments" the tuple (offsets, ids, a, b) as numpy arrays."""
+        o32, n32 = np.asarray(origin, np.float32).reshape(3), np.asarray(normal, np.float32).reshape(3)
+        h32 = np.asarray(heights, np.float32).reshape(-1)
+        pts = o32[None, :] + h32[:, None] * n32[None, :]
+        return self.sectionPlanes(pts, np.broadcast_to(n32, pts.shape), mode=mode, counters=counters)
+
     def closestPointsDevice(self, points_ptr: int, n: int, out_ptr: int, counters=None, flags=0) -> int:
         """bm_scene_closest_points on device pointers (n bm_point records of 16 bytes in, n bm_hit records of
         16 bytes out, both 16-byte aligned); returns the error code. Asynchronous on the context stream unless
@@ -1588,6 +1709,57 @@ class Model:
 
 
 _FPtr = C.POINTER(C.c_float)
+
+
+def chainSegments(a, b):
+    """Chains the cut segments of one plane (sectionPlanes mode "segments": a (m,3), b (m,3), numpy or torch)
+    into polylines on the host: (loops, chains), each a list of lists of segment indices into a and b.
+
+    Segments of length zero (a[i] and b[i] the same bytes: a triangle touching the plane from below in one
+    vertex) are dropped. The others are linked where the end b of one equals the start a of another byte for
+    byte: no tolerance, which is what the query's cut points allow. Where several segments start at one point,
+    the segments ending there are paired with them both in ascending input order (the k-th ending with the k-th
+    starting). Every segment then has at most one successor and one predecessor: a loop is a closed run,
+    listed from its lowest index; a chain is an open run, listed from its first segment to its last. Chains
+    come first by their first segment's index, loops by their lowest. A closed consistently oriented mesh gives
+    loops alone."""
+    def host(x):
+        if hasattr(x, "detach"):
+            x = x.detach().cpu().numpy()
+        return np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)
+    a, b = host(a), host(b)
+    if a.shape != b.shape:
+        raise BeamError(ERROR_INVALID_PARAMETER, "chainSegments: a and b are (m, 3) arrays of the same length")
+    ka = [r.tobytes() for r in a.view(np.uint32)]
+    kb = [r.tobytes() for r in b.view(np.uint32)]
+    live = [i for i in range(len(ka)) if ka[i] != kb[i]]
+    starts, ends = {}, {}
+    for i in live:  # ascending
+        starts.setdefault(ka[i], []).append(i)
+        ends.setdefault(kb[i], []).append(i)
+    nxt, has_prev = {}, set()
+    for key, incoming in ends.items():
+        for i, j in zip(incoming, starts.get(key, ())):
+            nxt[i] = j
+            has_prev.add(j)
+    loops, chains, seen = [], [], set()
+    for i in live:
+        if i in has_prev:
+            continue
+        run = [i]
+        while run[-1] in nxt:
+            run.append(nxt[run[-1]])
+        seen.update(run)
+        chains.append(run)
+    for i in live:
+        if i in seen:
+            continue
+        run = [i]
+        while nxt[run[-1]] != i:
+            run.append(nxt[run[-1]])
+        seen.update(run)
+        loops.append(run)
+    return loops, chains
 
 
 def reachable_records(records: np.ndarray) -> np.ndarray:

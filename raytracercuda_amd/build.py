@@ -15,7 +15,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libbeam_hip.so")
 SOURCES = ["bm_api.cpp", "bm_obj.cpp", "bm_rccl.cpp", "bm_build.hip", "bm_trace.hip", "bm_trace_ab.hip", "bm_kd.hip",
            "bm_gather.hip", "bm_rays.hip", "bm_points.hip", "bm_attrs.hip", "bm_xform.hip", "bm_multihit.hip",
-           "bm_points_multi.hip", "bm_boxes.hip", "bm_tris.hip", "bm_sweep.hip", "bm_normals.hip", "bm_signed.hip"]  # bm_trace_ab.hip is empty unless an A/B build defines BM_TRACE_AB=1
+           "bm_points_multi.hip", "bm_boxes.hip", "bm_tris.hip", "bm_sweep.hip", "bm_normals.hip", "bm_signed.hip", "bm_planes.hip"]  # bm_trace_ab.hip is empty unless an A/B build defines BM_TRACE_AB=1
 HEADERS = ["bm_common.h", "bm_internal.h", "bm_bdiag.h", "bm_sort.h", "bm_trace_dev.h", "bm_trace_lanes.h",
            "bm_trace_quad.h", "bm_trace_packet.h", "bm_query_dev.h", "bm_sat_dev.h", "bm_tritri_dev.h", "bm_sweep_dev.h",
            os.path.join("..", "..", "include", "beam_c.h")]

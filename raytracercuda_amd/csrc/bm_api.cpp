@@ -2474,6 +2474,86 @@ int32_t bm_scene_overlap_triangles_counters(bm_scene* s, const bm_tri* tris_dev,
     return tris_impl(s, tris_dev, n, mode, flags, out_dev, offsets_dev, ids_dev, out);
 }
 
+// ---- the per-mesh table of the hit-attribute and plane-section kernels ---------------------------------
+// attr_table_image: the table's byte image (one AttrMesh per scene mesh, then their offsets packed) for the
+// meshes as they are now, which must still be the build's; reqs (may be null): the slot requests whose
+// component counts are checked against each mesh. attr_table_upload: puts the image on the device on stream
+// st when it differs from the last one uploaded.
+static int32_t attr_table_image(bm_scene* s, const std::string& who, const bm::AttrReq* reqs, uint32_t num_reqs,
+                                std::vector<unsigned char>& image) {
+    bm_context* ctx = s->ctx;
+    // the table below describes the meshes as they are now: they must still be the build's
+    bool same = s->built_with.size() == s->meshes.size();
+    for (size_t i = 0; same && i < s->meshes.size(); ++i)
+        same = s->built_with[i].first == s->meshes[i] && s->built_with[i].second == s->meshes[i]->num_indices / 3;
+    if (!same)
+        return fail(ctx, BM_ERROR_NOT_BUILT,
+                    who + " needs the meshes and triangle counts of the last build (call updateGPUScene)");
+    const size_t nm = s->meshes.size();
+    image.assign((sizeof(bm::AttrMesh) + sizeof(uint32_t)) * nm, 0);
+    bm::AttrMesh* tab = reinterpret_cast<bm::AttrMesh*>(image.data());
+    uint32_t* offs = reinterpret_cast<uint32_t*>(image.data() + sizeof(bm::AttrMesh) * nm);
+    uint32_t have[BM_VERTEX_DATA_COUNT] = {};  // meshes carrying each slot
+    uint32_t off = 0;
+    for (size_t i = 0; i < nm; ++i) {
+        const bm_mesh* m = s->meshes[i];
+        if (m->num_indices && (!m->idx.p || m->max_index >= m->num_vertices))
+            return fail(ctx, BM_ERROR_INVALID_PARAMETER, "index out of range of the mesh's vertices");
+        bm::AttrMesh d{};
+        d.idx = m->idx.as<const uint32_t>();
+        d.tri_offset = off;
+        d.num_tris = m->num_indices / 3;
+        for (uint32_t k = 0; k < BM_VERTEX_DATA_COUNT; ++k) {
+            const bool has = m->slot[k].p && m->slot_comp[k];
+            d.slot[k] = has ? m->slot[k].as<const float>() : nullptr;
+            have[k] += has;
+        }
+        const bm_scene::Entry& en = s->entries[i];
+        if (en.inst) {
+            // world-space positions and normals, as of the last build or refit: the pools hold built_nv vertices
+            if (m->num_indices && m->max_index >= en.built_nv)
+                return fail(ctx, BM_ERROR_NOT_BUILT,
+                            who + ": an instance's mesh indexes vertices past those of the last build or refit");
+            d.slot[BM_VERTEX_DATA_POSITION] = s->inst_pos.as<const float>() + en.pool_off;
+            d.slot[BM_VERTEX_DATA_NORMAL] = s->inst_nrm.as<const float>() + en.pool_off;
+        }
+        for (uint32_t r = 0; r < num_reqs; ++r)
+            if (reqs[r].kind == bm::ATTR_SLOT && d.slot[reqs[r].slot] && m->slot_comp[reqs[r].slot] != reqs[r].comps)
+                return fail(ctx, BM_ERROR_INVALID_FORMAT, who + ": a mesh has the slot with another number of components");
+        std::memcpy(tab + i, &d, sizeof(d));
+        offs[i] = off;
+        off += d.num_tris;
+    }
+    for (uint32_t r = 0; r < num_reqs; ++r)
+        if (reqs[r].kind == bm::ATTR_SLOT && nm && !have[reqs[r].slot])
+            return fail(ctx, BM_ERROR_INVALID_FORMAT, who + ": no mesh of the scene has the slot");
+    if (off != s->n) return fail(ctx, BM_ERROR_NOT_BUILT, who + ": triangle count differs from the build's");
+    return BM_ERROR_ALL_FINE;
+}
+
+static int32_t attr_table_upload(bm_scene* s, std::vector<unsigned char>&& image, hipStream_t st) {
+    bm_context* ctx = s->ctx;
+    if (!image.empty() && image != s->attr_host) {
+        s->attr_host.clear();  // unknown until the new image is on its way
+        if (!s->attr_done) BM_HIP(ctx, hipEventCreateWithFlags(&s->attr_done, hipEventDisableTiming));
+        else BM_HIP(ctx, hipEventSynchronize(s->attr_done));  // the previous upload still reads the staging area
+        if (image.size() > s->attr_staging_cap) {
+            if (s->attr_staging) (void)hipHostFree(s->attr_staging);
+            s->attr_staging = nullptr;
+            s->attr_staging_cap = 0;
+            BM_HIP(ctx, hipHostMalloc((void**)&s->attr_staging, image.size(), hipHostMallocDefault));
+            s->attr_staging_cap = image.size();
+        }
+        GrowGuard grow{ctx};  // an earlier query still queued may read the old table
+        BM_HIP(ctx, grow.reserve(s->attr_table, image.size()));
+        std::memcpy(s->attr_staging, image.data(), image.size());
+        BM_HIP(ctx, hipMemcpyAsync(s->attr_table.p, s->attr_staging, image.size(), hipMemcpyHostToDevice, st));
+        BM_HIP(ctx, hipEventRecord(s->attr_done, st));
+        s->attr_host = std::move(image);
+    }
+    return BM_ERROR_ALL_FINE;
+}
+
 // ---- hit attributes (bm_attrs.hip) ---------------------------------------------------------------
 int32_t bm_scene_hit_attributes(bm_scene* s, const bm_hit* hits_dev, uint32_t n, const bm_attr_req* reqs,
                                 uint32_t num_reqs) {
@@ -2513,74 +2593,13 @@ int32_t bm_scene_hit_attributes(bm_scene* s, const bm_hit* hits_dev, uint32_t n,
     if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
     if (s->kd || s->hash || s->width != 4)
         return fail(ctx, BM_ERROR_INVALID_PARAMETER, "hit_attributes: BVH4 scenes only (no reference mode, BVH2 or BVH8)");
-    // the table below describes the meshes as they are now: they must still be the build's
-    bool same = s->built_with.size() == s->meshes.size();
-    for (size_t i = 0; same && i < s->meshes.size(); ++i)
-        same = s->built_with[i].first == s->meshes[i] && s->built_with[i].second == s->meshes[i]->num_indices / 3;
-    if (!same)
-        return fail(ctx, BM_ERROR_NOT_BUILT,
-                    "hit_attributes needs the meshes and triangle counts of the last build (call updateGPUScene)");
+    std::vector<unsigned char> image;
+    if (const int32_t e = attr_table_image(s, "hit_attributes", p.req, num_reqs, image)) return e;
     const size_t nm = s->meshes.size();
-    std::vector<unsigned char> image((sizeof(bm::AttrMesh) + sizeof(uint32_t)) * nm);
-    bm::AttrMesh* tab = reinterpret_cast<bm::AttrMesh*>(image.data());
-    uint32_t* offs = reinterpret_cast<uint32_t*>(image.data() + sizeof(bm::AttrMesh) * nm);
-    uint32_t have[BM_VERTEX_DATA_COUNT] = {};  // meshes carrying each slot
-    uint32_t off = 0;
-    for (size_t i = 0; i < nm; ++i) {
-        const bm_mesh* m = s->meshes[i];
-        if (m->num_indices && (!m->idx.p || m->max_index >= m->num_vertices))
-            return fail(ctx, BM_ERROR_INVALID_PARAMETER, "index out of range of the mesh's vertices");
-        bm::AttrMesh d{};
-        d.idx = m->idx.as<const uint32_t>();
-        d.tri_offset = off;
-        d.num_tris = m->num_indices / 3;
-        for (uint32_t k = 0; k < BM_VERTEX_DATA_COUNT; ++k) {
-            const bool has = m->slot[k].p && m->slot_comp[k];
-            d.slot[k] = has ? m->slot[k].as<const float>() : nullptr;
-            have[k] += has;
-        }
-        const bm_scene::Entry& en = s->entries[i];
-        if (en.inst) {
-            // world-space positions and normals, as of the last build or refit: the pools hold built_nv vertices
-            if (m->num_indices && m->max_index >= en.built_nv)
-                return fail(ctx, BM_ERROR_NOT_BUILT,
-                            "hit_attributes: an instance's mesh indexes vertices past those of the last build or refit");
-            d.slot[BM_VERTEX_DATA_POSITION] = s->inst_pos.as<const float>() + en.pool_off;
-            d.slot[BM_VERTEX_DATA_NORMAL] = s->inst_nrm.as<const float>() + en.pool_off;
-        }
-        for (uint32_t r = 0; r < num_reqs; ++r)
-            if (p.req[r].kind == bm::ATTR_SLOT && d.slot[p.req[r].slot] && m->slot_comp[p.req[r].slot] != p.req[r].comps)
-                return fail(ctx, BM_ERROR_INVALID_FORMAT,
-                            "hit_attributes: a mesh has the slot with another number of components");
-        std::memcpy(tab + i, &d, sizeof(d));
-        offs[i] = off;
-        off += d.num_tris;
-    }
-    for (uint32_t r = 0; r < num_reqs; ++r)
-        if (p.req[r].kind == bm::ATTR_SLOT && nm && !have[p.req[r].slot])
-            return fail(ctx, BM_ERROR_INVALID_FORMAT, "hit_attributes: no mesh of the scene has the slot");
-    if (off != s->n) return fail(ctx, BM_ERROR_NOT_BUILT, "hit_attributes: triangle count differs from the build's");
     if (n == 0) return BM_ERROR_ALL_FINE;
     BM_HIP(ctx, hipSetDevice(ctx->device));
     const hipStream_t st = ctx->stream;
-    if (nm && image != s->attr_host) {
-        s->attr_host.clear();  // unknown until the new image is on its way
-        if (!s->attr_done) BM_HIP(ctx, hipEventCreateWithFlags(&s->attr_done, hipEventDisableTiming));
-        else BM_HIP(ctx, hipEventSynchronize(s->attr_done));  // the previous upload still reads the staging area
-        if (image.size() > s->attr_staging_cap) {
-            if (s->attr_staging) (void)hipHostFree(s->attr_staging);
-            s->attr_staging = nullptr;
-            s->attr_staging_cap = 0;
-            BM_HIP(ctx, hipHostMalloc((void**)&s->attr_staging, image.size(), hipHostMallocDefault));
-            s->attr_staging_cap = image.size();
-        }
-        GrowGuard grow{ctx};  // an earlier query still queued may read the old table
-        BM_HIP(ctx, grow.reserve(s->attr_table, image.size()));
-        std::memcpy(s->attr_staging, image.data(), image.size());
-        BM_HIP(ctx, hipMemcpyAsync(s->attr_table.p, s->attr_staging, image.size(), hipMemcpyHostToDevice, st));
-        BM_HIP(ctx, hipEventRecord(s->attr_done, st));
-        s->attr_host = std::move(image);
-    }
+    if (const int32_t e = attr_table_upload(s, std::move(image), st)) return e;
     p.hits = reinterpret_cast<const float4*>(hits_dev);
     p.n = n;
     p.num_tris = s->n;
@@ -2590,6 +2609,88 @@ int32_t bm_scene_hit_attributes(bm_scene* s, const bm_hit* hits_dev, uint32_t n,
     p.num_reqs = num_reqs;
     BM_HIP(ctx, bm::launch_hit_attrs(p, st));
     return BM_ERROR_ALL_FINE;
+}
+
+// ---- plane section queries (bm_planes.hip) -------------------------------------------------------
+// boxes_impl's path and order of checks, then bm_scene_hit_attributes' check that the meshes are still the
+// build's and its table: the sides are taken on the meshes' own vertices. LIST writes ids, segments or both.
+static int32_t planes_impl(bm_scene* s, const bm_plane* planes, uint32_t n, uint32_t mode, uint32_t flags, void* out,
+                           const uint32_t* offsets, uint32_t* ids, bm_segment* segs, uint64_t* counters) {
+    if (!s) return BM_ERROR_INVALID_PARAMETER;
+    bm_context* ctx = s->ctx;
+    const std::string who = "section_planes: ";
+    const bool list = mode == BM_PLANES_LIST;
+    if (n && (!planes || (!list && !out) || (list && (!offsets || (!ids && !segs)))))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "null plane, result or offset pointer, or neither ids nor segments");
+    if ((reinterpret_cast<uintptr_t>(planes) & 15u) ||
+        (list && (((reinterpret_cast<uintptr_t>(offsets) | reinterpret_cast<uintptr_t>(ids)) & 3u) ||
+                  (reinterpret_cast<uintptr_t>(segs) & 15u))) ||
+        (mode != BM_PLANES_ANY && (reinterpret_cast<uintptr_t>(out) & 3u)))
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER,
+                    who + "plane and segment pointers must be 16-byte aligned, count, offset and id pointers 4-byte");
+    if (mode > BM_PLANES_LIST || flags != 0)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "unknown mode or flag bits");
+    if (ctx->reference_kd || ctx->reference_hash || ctx->bvh_width != 4)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    if (!s->built) return fail(ctx, BM_ERROR_NOT_BUILT, "scene has no current build (call updateGPUScene)");
+    if (s->kd || s->hash || s->width != 4)
+        return fail(ctx, BM_ERROR_INVALID_PARAMETER, who + "BVH4 scenes only (no reference mode, BVH2 or BVH8)");
+    std::vector<unsigned char> image;
+    if (const int32_t e = attr_table_image(s, "section_planes", nullptr, 0, image)) return e;
+    const size_t nm = s->meshes.size();
+    for (size_t i = 0; i < nm; ++i)  // a mesh with triangles was built from its positions: three floats each
+        if (s->meshes[i]->num_indices && s->meshes[i]->slot_comp[BM_VERTEX_DATA_POSITION] != 3)
+            return fail(ctx, BM_ERROR_INVALID_FORMAT, who + "a mesh has no 3-component position slot");
+    if (counters) std::fill(counters, counters + 4, uint64_t(0));
+    if (n == 0) return BM_ERROR_ALL_FINE;
+    BM_HIP(ctx, hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    if (const int32_t e = attr_table_upload(s, std::move(image), st)) return e;
+    bm::TraceParams p{};
+    p.nodes = s->records.as<const uint4>();
+    p.tris = s->tris.as<const float4>();
+    p.num_tris = s->n;
+    p.variant = bm::TRACE_QUAD;
+    p.bvh_width = 4;
+    p.prio_after = ctx->prio_after;
+    p.prio_level = ctx->prio_level;
+    p.q_rays = reinterpret_cast<const float4*>(planes);
+    p.q_out = out;
+    p.q_n = n;
+    p.q_ent = list ? offsets : nullptr;  // launch_section_planes: the segment offsets and the ids
+    p.q_counts = list ? ids : nullptr;
+    bm::PlaneParams x{};
+    x.meshes = nm ? s->attr_table.as<const bm::AttrMesh>() : nullptr;
+    x.offsets = nm ? reinterpret_cast<const uint32_t*>(s->attr_table.as<const unsigned char>() + sizeof(bm::AttrMesh) * nm)
+                   : nullptr;
+    x.num_meshes = (uint32_t)nm;
+    x.segs = list ? reinterpret_cast<float4*>(segs) : nullptr;
+    if (const int32_t e = reserve_overflow(ctx, nullptr, st, p)) return e;
+    if (counters) {
+        if (!ctx->rays_counters) BM_HIP(ctx, hipMalloc(&ctx->rays_counters, 4 * sizeof(unsigned long long)));
+        BM_HIP(ctx, hipMemsetAsync(ctx->rays_counters, 0, 4 * sizeof(unsigned long long), st));
+        p.counters = ctx->rays_counters;
+    }
+    BM_HIP(ctx, bm::launch_section_planes(p, x, mode, counters != nullptr, st));
+    if (counters) {
+        unsigned long long h[4];
+        BM_HIP(ctx, hipMemcpyAsync(h, ctx->rays_counters, sizeof(h), hipMemcpyDeviceToHost, st));
+        BM_HIP(ctx, hipStreamSynchronize(st));
+        std::copy(h, h + 4, counters);
+    }
+    return BM_ERROR_ALL_FINE;
+}
+
+int32_t bm_scene_section_planes(bm_scene* s, const bm_plane* planes_dev, uint32_t n, uint32_t mode, uint32_t flags,
+                                void* out_dev, const uint32_t* offsets_dev, uint32_t* ids_dev, bm_segment* segs_dev) {
+    return planes_impl(s, planes_dev, n, mode, flags, out_dev, offsets_dev, ids_dev, segs_dev, nullptr);
+}
+
+int32_t bm_scene_section_planes_counters(bm_scene* s, const bm_plane* planes_dev, uint32_t n, uint32_t mode,
+                                         uint32_t flags, void* out_dev, const uint32_t* offsets_dev, uint32_t* ids_dev,
+                                         bm_segment* segs_dev, uint64_t out[4]) {
+    if (!out) return BM_ERROR_INVALID_PARAMETER;
+    return planes_impl(s, planes_dev, n, mode, flags, out_dev, offsets_dev, ids_dev, segs_dev, out);
 }
 
 static TraceReq bands_req(uint32_t band_height, uint32_t band_step, uint32_t band_first) {

@@ -298,6 +298,22 @@ struct AttrParams {
 };
 hipError_t launch_hit_attrs(const AttrParams& p, hipStream_t s);
 
+// ---- plane section queries (bm_planes.hip): the triangles each plane crosses and their cut segments ----
+// What the query needs beyond TraceParams, as the kernel's second argument (TraceParams stays as it is): the
+// hit-attribute table, since the sides are taken on the meshes' own vertices, and the segment records.
+struct PlaneParams {
+    const AttrMesh* meshes;   // num_meshes entries; slot[BM_VERTEX_DATA_POSITION]: the positions read
+    const uint32_t* offsets;  // their tri_offset again, packed for the search
+    uint32_t num_meshes;
+    uint32_t pad;
+    float4* segs;             // BM_PLANES_LIST: bm_segment records, two float4 each; may be null
+};
+// For each of p.q_n planes, two float4 (point, pad) (normal, pad) each in p.q_rays; set up as for
+// launch_overlap_boxes, under the same names: p.q_out counts or bytes, p.q_ent the LIST offsets, p.q_counts the
+// LIST ids (may be null when x.segs is not). count: into p.counters[0..3] (node records, triangle tests, the
+// sum of the counts, the deepest stack held).
+hipError_t launch_section_planes(const TraceParams& p, const PlaneParams& x, uint32_t mode, bool count, hipStream_t s);
+
 // ---- instance transforms (bm_xform.hip): world-space copies of instanced meshes' positions and normals ----
 // One row per instance entry of the scene, in scene order; uploaded as a byte image, followed by the rows'
 // unit_first again, packed for the search.
